@@ -1,10 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: Mrays/s of the MI355X ray march on a BASELINE.json config (default
-C2, the headline: 256^3 synthetic grid, VCS + original, 1920x1080), plus the
-roofline of the dominant kernel and the CPU oracle baseline.
+C2, the headline: 256^3 synthetic grid, VCS + original, 1920x1080); with --full
+also the roofline of the dominant kernel and the CPU oracle baseline.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5]
-                  [--tiling auto|weak|fixed]
+                  [--tiling auto|weak|fixed] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the scene, deals the
+frame (N > 1: learns the strips), renders W warmup steps and SETTLE_LAUNCHES untimed launches
+of the view, times K steps, writes the last step's frame if --dump-outputs is given (the
+scene, camera and lights are the same in every run, so two builds compare frame for frame)
+and prints the line: `metric`, `value`, `ms_per_step`, the workload.  Everything below about
+`kernel_ms*`, the roofline, the moving view, the N > 1 frame latencies, the latency cut and the
+CPU baseline is measured -- and printed -- with --full only (runs of their own before and
+after the timed loop; the line's `full` says which kind of run it was).
 
 A step = one full frame.  With N > 1 ranks the frame is dealt over the ranks --
 fixed tiling: learned strips (round 6: rank r renders one contiguous strip of rows, the
@@ -104,6 +113,13 @@ def parse():
     p.add_argument("--dump-frame", default="",
                    help="rank 0 saves the last frame of the timed loop (.npy): RGB8 [H, W, 3] with N > 1 ranks, "
                         "packed 0x00RRGGBB words [H, W] with one")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes what the timed loop's last step computed to DIR/frame_rgb.npy: the frame "
+                        "as float32 [H, W, 3] (R, G, B in 0..255); a frame over 64 MB is written as a fixed, "
+                        "seeded sample of its pixels [DUMP_SAMPLE, 3]")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: one launch alone (kernel_ms*), the "
+                        "roofline, the moving view, N > 1 frame latencies and the latency cut, the CPU baseline")
     return p.parse_args()
 
 
@@ -147,6 +163,29 @@ HEADLINE = "Mrays/sec at 1920x1080, 256^3 grid (VCS+original); achieved HBM GB/s
 STRIP_ITERS, STRIP_WARM, STRIP_STEPS, STRIP_ALIGN = 12, 16, 80, 4
 # the latency cut's lone frames per rank and round (after LAT_WARM untimed ones)
 LAT_WARM, LAT_REPS = 4, 7
+# a plain run's untimed launches of the view before its timed loop (each of the device's 16
+# launch slots sees the view 15 times; --full runs its isolated launches there instead)
+SETTLE_LAUNCHES = 240
+# --dump-outputs: at most DUMP_MAX_BYTES are written; a larger frame as DUMP_SAMPLE of its pixels
+DUMP_MAX_BYTES, DUMP_SAMPLE, DUMP_SEED = 64 * 1000 * 1000, 4 * 1000 * 1000, 20240601
+
+
+def dump_outputs(path: str, frame: np.ndarray) -> None:
+    """Write the frame the timed loop's last step left (BandGather.last_frame: packed
+    0x00RRGGBB words [H, W] with one rank, RGB8 [H, W, 3] after the N > 1 exchange) as
+    path/frame_rgb.npy: float32 [H, W, 3], R, G, B in 0..255 -- or, for a frame that would
+    take more than DUMP_MAX_BYTES, the same of DUMP_SAMPLE pixels [DUMP_SAMPLE, 3] drawn
+    once with a fixed seed (sorted row-major pixel indices: the same for every run)."""
+    if frame.ndim == 2:
+        w = frame.view(np.uint32)
+        frame = np.stack([(w >> 16) & 0xFF, (w >> 8) & 0xFF, w & 0xFF], axis=-1)
+    rgb = frame.reshape(frame.shape[0], frame.shape[1], 3)
+    if rgb.size * 4 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rgb.shape[0] * rgb.shape[1], DUMP_SAMPLE,
+                                                              replace=False))
+        rgb = rgb.reshape(-1, 3)[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame_rgb.npy"), np.ascontiguousarray(rgb, dtype=np.float32))
 
 
 def learn_strips(pipe, render_rows, W, H, world, rank, dev, stage_host, grouped) -> list:
@@ -407,19 +446,25 @@ def main():
         moving_step[0] += 1
     render_moving.vr_stream_arg = True
 
-    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
-    stats = torch.zeros(2, dtype=torch.int64, device=dev)
-    if strip:
-        vr.render_ex(scene, cfg.algorithm, cam, lit, info, W, H, pipe.bufs[0], *pipe.rows(), counter=ctr, stats=stats)
-    else:
-        vr.render_ex(scene, cfg.algorithm, cam, lit, info, W, H, pipe.bufs[0], band_rows=band_rows, rank=rank,
-                     nranks=world, counter=ctr, stats=stats, tile_cols=tcols)
-    torch.cuda.synchronize()
-    launch_bytes = int(ctr.item())
-    ff_iters, ff_bytes = (int(x) for x in stats.cpu().tolist())
-    issued_bytes = launch_bytes - ff_bytes
-    frame_bytes = int(allreduce(launch_bytes, dtype=torch.int64))
-    frame_issued = int(allreduce(issued_bytes, dtype=torch.int64))
+    def count_bytes():
+        ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        stats = torch.zeros(2, dtype=torch.int64, device=dev)
+        if strip:
+            vr.render_ex(scene, cfg.algorithm, cam, lit, info, W, H, pipe.bufs[0], *pipe.rows(), counter=ctr,
+                         stats=stats)
+        else:
+            vr.render_ex(scene, cfg.algorithm, cam, lit, info, W, H, pipe.bufs[0], band_rows=band_rows, rank=rank,
+                         nranks=world, counter=ctr, stats=stats, tile_cols=tcols)
+        torch.cuda.synchronize()
+        launch_bytes = int(ctr.item())
+        ff_iters, ff_bytes = (int(x) for x in stats.cpu().tolist())
+        issued_bytes = launch_bytes - ff_bytes
+        frame_bytes = int(allreduce(launch_bytes, dtype=torch.int64))
+        frame_issued = int(allreduce(issued_bytes, dtype=torch.int64))
+        return launch_bytes, ff_iters, issued_bytes, frame_bytes, frame_issued
+
+    if args.full:                               # (the roofline's numerator: --full only)
+        launch_bytes, ff_iters, issued_bytes, frame_bytes, frame_issued = count_bytes()
 
     for _ in range(args.warmup):
         pipe.step(render)
@@ -481,12 +526,20 @@ def main():
     # (before the timed loop: the learned orders of the device's 16 launch slots are made here --
     # after the timed loop instead, the loop's first frames make them, 0.1019-0.1057 -> 0.160 ms
     # per step at 20 steps, profiles/r06/driver/iso_after.txt)
-    ev, ev_grid, ev_first, n_iso = iso_phase()
+    if args.full:
+        ev, ev_grid, ev_first, n_iso = iso_phase()
+    else:
+        # A plain run times nothing here, but its timed loop needs the same start: the view's
+        # orders learned by every one of the device's 16 launch slots and the GPU at its loaded
+        # clock.  SETTLE_LAUNCHES untimed launches of the view on the launch stream make both.
+        for _ in range(SETTLE_LAUNCHES):
+            render(pipe.bufs[0])
+        torch.cuda.synchronize()
 
     # N > 1: latency of ONE frame, first launch -> gathered and assembled on
     # rank 0, without the overlap of the pipelined loop
     frame_latency_ms = None
-    if grouped:
+    if grouped and args.full:
         lat = []
         for _ in range(5):
             barrier()
@@ -510,31 +563,36 @@ def main():
     dt = time.perf_counter() - t0
     dt = allreduce(dt, op=dist.ReduceOp.MAX)
     ms_per_step = dt / args.steps * 1e3
-    kern_ms = ev[0].elapsed_time(ev[1]) / n_iso
-    kern_grid_ms = ev_grid[0].elapsed_time(ev_grid[1]) / n_iso
-    kern_first_ms = ev_first[0].elapsed_time(ev_first[1]) / n_iso
+    if args.full:
+        kern_ms = ev[0].elapsed_time(ev[1]) / n_iso
+        kern_grid_ms = ev_grid[0].elapsed_time(ev_grid[1]) / n_iso
+        kern_first_ms = ev_first[0].elapsed_time(ev_first[1]) / n_iso
     mrays = W * H / (ms_per_step * 1e-3) / 1e6
     if args.dump_frame and rank == 0:
         np.save(args.dump_frame, pipe.last_frame().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe.last_frame().cpu().numpy())
 
     # the same pipelined loop with the moving view (nothing learned; after the timed loop)
-    barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        pipe.step(render_moving)
-    pipe.drain()
-    torch.cuda.synchronize()
-    barrier()
-    dt_mov = allreduce(time.perf_counter() - t1, op=dist.ReduceOp.MAX)
-    ms_moving = dt_mov / args.steps * 1e3
+    ms_moving = None
+    if args.full:
+        barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            pipe.step(render_moving)
+        pipe.drain()
+        torch.cuda.synchronize()
+        barrier()
+        dt_mov = allreduce(time.perf_counter() - t1, op=dist.ReduceOp.MAX)
+        ms_moving = dt_mov / args.steps * 1e3
 
     # N > 1 with learned strips: a second cut, balanced on one frame's latency instead of the
     # pipelined rate, and the latency of one frame on it (after the timed loops: the strips and
     # the learned orders of their views change)
     frame_latency_cut_ms, lat_hist = None, []
     thr_strips = list(pipe.S) if strip else None
-    if strip and grouped:
+    if strip and grouped and args.full:
         lat_hist = learn_latency_strips(pipe, lambda buf, y0, y1: vr.render_ex(scene, cfg.algorithm, cam, lit, info,
                                                                                W, H, buf, y0, y1),
                                         W, H, world, rank, dev, stage_host, grouped)
@@ -556,7 +614,8 @@ def main():
             root, ext = os.path.splitext(args.dump_frame)
             np.save(root + ".latency_cut" + (ext or ".npy"), pipe.last_frame().cpu().numpy())
 
-    if rank == 0:
+    roof = None
+    if rank == 0 and args.full:
         def gbs(nbytes, ms):
             return nbytes / (ms * 1e-3) / 1e9
         # The roofline's numerator: the bytes this launch's walks stand for minus
@@ -651,6 +710,7 @@ def main():
         else:
             roof["bound"] = "valu" if cfg.store == vr.StorageType.VOXEL_CLUSTER_STORE else "hbm"
             roof["bound_basis"] = "no PMC profile of this config in profiles/traffic.json: by store"
+    if rank == 0:
         metric = HEADLINE if cfg.name == "C2" else \
             (f"Mrays/sec at {cfg.width}x{cfg.height}, {cfg.grid}^3 grid ({cfg.store.name}+{cfg.algorithm.name}); "
              f"achieved HBM GB/s")
@@ -673,11 +733,6 @@ def main():
             # orders (work order, lane order) and the crawl-pass skip apply (include/vr.h
             # vr_forget_orders); the moving view renders every frame from scratch
             "view": "repeated identical view (learned per-view work/lane orders and crawl skip apply)",
-            "value_moving_view": round(W * H / (ms_moving * 1e-3) / 1e6, 2),
-            "ms_per_step_moving_view": round(ms_moving, 4),
-            "moving_view_basis": "the same pipelined loop, steps frames, the camera eye moved by 1, 2, 3 ulps in "
-                                 "x in turn: no launch sees the view its predecessor or its slot's previous launch "
-                                 "saw, so nothing is learned (every frame a first render, as for a moving camera)",
             "higher_is_better": True,
             "scaling": "strong" if tiling == "fixed" else "weak",
             "vs_baseline": None,
@@ -691,26 +746,37 @@ def main():
                        "voxels": int(len(rgb)), "parallelism": par, "layout": "strips" if strip else ("tiles" if tcols else "bands"),
                        "frames_in_flight": pipe.depth,
                        "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")},
-            "kernel_ms": round(kern_ms, 4),
-            "kernel_ms_grid_order": round(kern_grid_ms, 4),
-            "kernel_ms_first_render": round(kern_first_ms, 4),
-            "kernel_ms_basis": f"{n_iso} launches one after the other on one stream, one HIP event pair around them "
-                               "(each: tile pass + crawl pass): kernel_ms with the AUTO schedule (heaviest tile "
-                               "groups first and the lane order, both learned from earlier launches of the same "
-                               "view), kernel_ms_grid_order in grid order with the learned lane order, "
-                               "kernel_ms_first_render with what the device learned dropped before every launch "
-                               "(vr_forget_orders: grid order, 8x8 tiles -- a first render)",
-            "kernel_mrays_per_s": round(W * H / world / (kern_first_ms * 1e-3) / 1e6, 2),
             "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
-            "roofline": roof,
-            # the non-instrumented launches of this run in order, per phase (a rocprofv3 kernel
-            # trace of the same command splits into them: profiles/roofline_phases.py)
-            "dispatch_phases": {"strip_calibration": STRIP_ITERS * (STRIP_WARM + STRIP_STEPS) if strip else 0,
-                                "warmup": args.warmup, "iso_first": n_iso, "untimed": 40, "iso_grid": n_iso,
-                                "iso_learned": n_iso,
-                                "latency": 5 if grouped else 0, "timed": args.steps, "moving": args.steps,
-                                "latency_cut": (STRIP_ITERS * (LAT_WARM + LAT_REPS) + 16 + 5) if lat_hist else 0},
+            "full": bool(args.full),
         }
+        if args.full:
+            line.update({
+                "value_moving_view": round(W * H / (ms_moving * 1e-3) / 1e6, 2),
+                "ms_per_step_moving_view": round(ms_moving, 4),
+                "moving_view_basis": "the same pipelined loop, steps frames, the camera eye moved by 1, 2, 3 ulps "
+                                     "in x in turn: no launch sees the view its predecessor or its slot's previous "
+                                     "launch saw, so nothing is learned (every frame a first render, as for a "
+                                     "moving camera)",
+                "kernel_ms": round(kern_ms, 4),
+                "kernel_ms_grid_order": round(kern_grid_ms, 4),
+                "kernel_ms_first_render": round(kern_first_ms, 4),
+                "kernel_ms_basis": f"{n_iso} launches one after the other on one stream, one HIP event pair around "
+                                   "them (each: tile pass + crawl pass): kernel_ms with the AUTO schedule (heaviest "
+                                   "tile groups first and the lane order, both learned from earlier launches of "
+                                   "the same view), kernel_ms_grid_order in grid order with the learned lane "
+                                   "order, kernel_ms_first_render with what the device learned dropped before "
+                                   "every launch (vr_forget_orders: grid order, 8x8 tiles -- a first render)",
+                "kernel_mrays_per_s": round(W * H / world / (kern_first_ms * 1e-3) / 1e6, 2),
+                "roofline": roof,
+                # the non-instrumented launches of this run in order, per phase (a rocprofv3 kernel
+                # trace of the same command splits into them: profiles/roofline_phases.py)
+                "dispatch_phases": {"strip_calibration": STRIP_ITERS * (STRIP_WARM + STRIP_STEPS) if strip else 0,
+                                    "warmup": args.warmup, "iso_first": n_iso, "untimed": 40, "iso_grid": n_iso,
+                                    "iso_learned": n_iso,
+                                    "latency": 5 if grouped else 0, "timed": args.steps, "moving": args.steps,
+                                    "latency_cut": (STRIP_ITERS * (LAT_WARM + LAT_REPS) + 16 + 5) if lat_hist
+                                    else 0},
+            })
         if strip:
             line["config"]["strip_bounds"] = thr_strips
             line["config"]["strip_calibration"] = strip_hist
@@ -726,7 +792,7 @@ def main():
             line["frame_latency_basis"] = ("frame_latency_ms: one frame first launch -> gathered on rank 0 on the "
                                            "throughput cut (config.strip_bounds); _latency_cut: the same on strips "
                                            "re-cut from the ranks' lone-frame times (config.latency_strip_bounds)")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, xyz, rgb, args.cpu_threads or baseline_threads())
         print(json.dumps(line), flush=True)
     if grouped:

@@ -22,8 +22,9 @@ for rnd in range(int(opts["--rounds"])):
         lib, _, extra = spec.partition(":")
         env = dict(os.environ, VR_LIBRARY=os.path.abspath(lib))
         env.update(kv.split("=", 1) for kv in extra.split(",") if kv)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--no-cpu-baseline",
-                            "--steps", opts["--steps"]], env=env, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--full",
+                            "--no-cpu-baseline", "--steps", opts["--steps"]], env=env, capture_output=True,
+                           text=True, timeout=600)
         js = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not js:
             print(f"[{rnd}] {os.path.basename(lib)}: FAILED {r.stderr[-400:]}", flush=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 kernel trace of ONE bench.py run into the run's dispatch phases and
+"""Split a rocprofv3 kernel trace of ONE `bench.py --full` run into the run's dispatch phases and
 recompute every roofline fraction of its JSON line from the trace alone.
 
   python profiles/roofline_phases.py <run_kernel_trace.csv> <bench_line.json> [out_dir]

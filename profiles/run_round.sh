@@ -9,7 +9,7 @@ TAG=${1:-r01}; CFG=${2:-C2}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 bench.py --config $CFG --no-cpu-baseline"
+BENCH="python3 bench.py --config $CFG --full --no-cpu-baseline"
 # counter passes: one frame at a time, so every dispatch's counters are its own
 PMCB="$BENCH --frames-in-flight 1"
 run() { timeout -k 10 400 "$@" >> "$OUT/log.txt" 2>&1; local rc=$?; if [ $rc -ne 0 ]; then echo "step failed rc=$rc: $*"; exit $rc; fi; }

@@ -50,7 +50,7 @@ def _run_bench(world, extra, tmp_path, W=480, H=270):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "4", "--warmup", "2", "--config", "C2", "--tiling", "fixed",
-           "--resolution", f"{W}x{H}", "--no-cpu-baseline", "--dump-frame", str(dump)] + extra
+           "--resolution", f"{W}x{H}", "--full", "--no-cpu-baseline", "--dump-frame", str(dump)] + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, f"bench.py over {world} ranks failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
@@ -85,7 +85,7 @@ def test_bench_frame_path_ranks_share_one_gpu(world, layout, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "4", "--warmup", "2", "--config", "C2", "--tiling", "fixed",
-           "--resolution", f"{W}x{H}", "--backend", "gloo", "--same-device", "--no-cpu-baseline",
+           "--resolution", f"{W}x{H}", "--backend", "gloo", "--same-device", "--full", "--no-cpu-baseline",
            "--layout", layout, "--dump-frame", str(dump)]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
