@@ -161,7 +161,7 @@ static int vrec_cmp(const void* a, const void* b) {
 /* Deterministic stand-in for Random::getRandomInt (Random.cuh:14-18); any
  * valid cuckoo placement yields identical lookup VALUES, but the
  * bytes a lookup reads depend on the table a key sits in (4 more for table 2),
- * so the stand-in is the product builder's (vr_host.cpp cuckoo_build): the same
+ * so the stand-in is the product builder's (vr_scene.cpp cuckoo_build): the same
  * LCG, seeded from the region's key count and first key. */
 static uint32_t lcg_next(uint64_t* s) {
     *s = *s * 6364136223846793005ull + 1442695040888963407ull;

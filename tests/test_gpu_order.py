@@ -1,4 +1,4 @@
-"""GPU test of the tile pass's heaviest-first work order (vr_host.cpp, KView::order):
+"""GPU test of the tile pass's heaviest-first work order (vr_launch.cpp, KView::order):
 each launch slot keeps an order of the tile groups made from the costs an earlier
 launch of that slot recorded, and the tile pass renders tile group order[i] in
 workgroup i.  Any permutation must render the same pixels, including an order made

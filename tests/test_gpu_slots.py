@@ -1,7 +1,7 @@
-"""GPU test of the per-launch scratch slots (vr_host.cpp SlotRing): each slot's
+"""GPU test of the per-launch scratch slots (vr_launch.cpp SlotRing): each slot's
 crawl-pass deferral list and its work-order buffers, fenced by per-slot events;
 both passes of a launch run on the launch's own stream (with launches in flight
-the crawl pass takes 8 records per wave).  Many launches in flight on several
+the crawl pass takes 32 records per wave).  Many launches in flight on several
 streams at once, far more of them than the ring has slots, must each render
 exactly the frame one serial launch renders: a slot shared by two launches in
 flight would mix their deferred records (wrong or zero pixels), and a missing
@@ -59,7 +59,7 @@ def test_launches_in_flight_on_three_streams(c5_scene, kernel, algo):
 
 
 def test_crawl_skip_safety_net(c5_scene):
-    """The crawl-pass skip's safety net (vr_host.cpp launch, vr_march.hip deferral_report).
+    """The crawl-pass skip's safety net (vr_launch_plan.h CrawlSkip, vr_march.hip deferral_report).
     Every slot first learns a view that defers nothing (C5's top rows: each slot's last crawl
     pass reports 0).  Then the next launch is forced to skip its crawl pass on C5's crawl rows,
     as a wrong skip would: its deferred pixels stay 0 (the frame differs).  Its tile pass
@@ -95,7 +95,7 @@ def test_crawl_skip_safety_net(c5_scene):
 
 
 def test_crawl_skip_key_inputs(c5_scene):
-    """The crawl-pass skip is keyed by everything that decides deferral (vr_host.cpp view_key,
+    """The crawl-pass skip is keyed by everything that decides deferral (vr_launch.cpp view_key,
     crawl_key): one camera and row range, rendered 40 times with TILE and TILE_REWALK
     alternating on a scene where it defers nothing (the C2 grid: every slot learns to skip),
     then 40 times on C5's scene, where the same view defers thousands of crawling rays, then

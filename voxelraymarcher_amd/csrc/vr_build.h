@@ -1,4 +1,4 @@
-// vr_build.h -- the GPU scene builder (vr_build.hip), used by vr_host.cpp.
+// vr_build.h -- the GPU scene builder (vr_build.hip), used by vr_scene.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

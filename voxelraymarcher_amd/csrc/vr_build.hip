@@ -2,7 +2,7 @@
 // VoxelSceneCPU::insertVoxel / generateVoxelScene (VoxelSceneCPU.cuh:16-93),
 // the VoxelClusterStore image (VoxelClusterStore.cuh:37-85) and the
 // CuckooHashTable images (CuckooHashTable.cuh:20-49, 97-178), producing the
-// same device layout as the host builder in vr_host.cpp (vr_internal.h):
+// same device layout as the host builder in vr_scene.cpp (vr_internal.h):
 //
 //   1. region coordinates, the min/max coordinate (minCoord/maxCoord start at 0)
 //      and the first colour above 24 bits                       (reduction)

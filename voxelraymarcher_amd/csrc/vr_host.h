@@ -1,0 +1,85 @@
+// vr_host.h -- what the host translation units of libvr.so share (vr_host.cpp, vr_scene.cpp,
+// vr_scene_io.cpp, vr_launch.cpp).  Private: nothing declared here is exported.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "vr.h"
+#include "vr_internal.h"
+
+#pragma GCC visibility push(hidden)
+
+namespace vr {
+
+inline int fail(int code, const std::string& msg) { return set_error(code, msg); }
+inline int hip_fail(hipError_t e, const char* what) {
+    return fail(VR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// FNV-1a over n bytes, continuing from h (kFnvBasis to start).
+constexpr uint64_t kFnvBasis = 1469598103934665603ull;
+inline uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = (const unsigned char*)p;
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+}  // namespace vr
+
+struct vr_scene {
+    // a process-unique id (the learned orders' view key: a later scene may reuse a freed
+    // scene's address), drawn by vr_scene.cpp
+    const uint64_t serial;
+    explicit vr_scene(uint64_t id) : serial(id) {}
+    int device = 0;
+    vr_store store = VR_STORE_VCS;
+    uint32_t D = 1;
+    int32_t min_coord = 0;
+    uint32_t n_regions = 0;
+    uint64_t n_voxels = 0;
+    vr::DevBuf region_slot, vcs_mask, vcs_vals, ht_meta, ht_slots;
+    vr::DevBuf vcs_cbits;   // derived (not part of vr_scene_digest): cluster-existence bits per region
+    vr::DevBuf ht_filter;   // derived (not part of vr_scene_digest): cuckoo key-presence bits per region
+    uint64_t device_bytes() const {
+        return region_slot.bytes + vcs_mask.bytes + vcs_vals.bytes + ht_meta.bytes + ht_slots.bytes + vcs_cbits.bytes +
+               ht_filter.bytes;
+    }
+};
+
+namespace vr {
+
+// vr_scene.cpp
+KScene kscene(const vr_scene* s);
+int build_scene(int device, vr_store store, const int32_t* xyz, const uint32_t* rgb, size_t n, bool on_device,
+                vr_build mode, void* stream, vr_scene** out);
+
+// vr_scene_io.cpp: a scene file's voxels (.vxb or .vox CSV, read and parsed once)
+struct VoxParse {
+    std::vector<int32_t> xyz;
+    std::vector<uint32_t> rgb;
+};
+int read_voxels(const char* path, VoxParse& out);
+
+}  // namespace vr
+
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// vr_internal.h -- layouts shared by the host builder (vr_host.cpp) and the
+// vr_internal.h -- layouts shared by the host builder (vr_scene.cpp) and the
 // HIP kernels (vr_march.hip).  See DESIGN.md "Data layout in HBM".
 #pragma once
 
@@ -114,7 +114,7 @@ struct KView {
     uint32_t tile_minv;       // floor(2^32 / tile_cols) (2^32 - 1 for 1)
     uint32_t col_R, col_rank, col_stride;   // 2-D deal: ranks, this rank, stride (< col_R)
     // ---- end of the view's identity.  Everything above `out` is hashed, with the scene and
-    // the algorithm, into the view key (vr_host.cpp view_key) under which the learned orders
+    // the algorithm, into the view key (vr_launch.cpp view_key) under which the learned orders
     // and the crawl-pass skip are kept: a field that changes any pixel, or which pixels the
     // tile pass defers to the crawl pass, MUST sit above this line.  Everything below is a
     // per-launch buffer or a launch knob that changes neither (checked by the static_assert
@@ -128,7 +128,7 @@ struct KView {
     uint32_t* defer;         // crawl deferral slot: [count, done, overflow, 0, records (kDeferRecWords each)...]
     uint32_t defer_cap;
     uint32_t crawl_rewalk;    // 1: deferred crawls are walked from the pixel's start (VR_KERNEL_TILE_REWALK)
-    uint32_t crawl_rpw;       // crawl records per wave (0 = 4): 2 for a lone frame, 8 with frames in flight
+    uint32_t crawl_rpw;       // crawl records per wave (0 = 4): 2 for a lone frame, 32 with frames in flight
     uint32_t* defer_stat;     // host-mapped word: the crawl pass writes its record count there (grid sizing)
     // Tile-pass work order ("Heaviest tiles first"): workgroup i of the grid
     // renders tile order[i] = (tile row << 16 | tile column) -- a permutation of the grid
@@ -154,7 +154,7 @@ struct KView {
 // The per-launch tail of KView (see "end of the view's identity" above): out, bytes, stats,
 // defer, defer_cap, crawl_rewalk, crawl_rpw, defer_stat, order, cost, perm, pcost, slot_stat,
 // launch_id.  defer_cap and crawl_rewalk change only how deferred pixels are resumed, never
-// which ones defer; the crawl-pass skip keys them anyway (vr_host.cpp crawl_key).
+// which ones defer; the crawl-pass skip keys them anyway (vr_launch.cpp crawl_key).
 // (10 pointers, 4 words, padding: 104 bytes)
 static_assert(sizeof(KView) - offsetof(KView, out) == 104,
               "a KView field was added after `out`: review whether it belongs to the view identity");
@@ -172,7 +172,7 @@ static_assert(sizeof(KView) - offsetof(KView, out) == 104,
 //   11-13 tX, tY, tZ of the last voxel step (hit normal; 0 for shadow walks)
 //   14 reserved (0)           15-17 the crawl iteration's voxel (filled in by the crawl pass)
 //   18 lit colour             19 unused
-// A slot is used by one launch at a time (vr_host.cpp SlotRing).
+// A slot is used by one launch at a time (vr_launch.cpp SlotRing).
 constexpr uint32_t kDeferCap = 16384;
 constexpr uint32_t kDeferRecWords = 20;
 constexpr uint32_t kDeferWords = 4 + kDeferCap * kDeferRecWords;

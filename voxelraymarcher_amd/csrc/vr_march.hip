@@ -271,7 +271,7 @@ constexpr uint32_t kDeferredIters = 0xFFFFFFFFu;
 // host-mapped report word (KView::slot_stat): {launch id, 1}.  On a launch that runs its
 // crawl pass the pass overwrites it with its own count.  On a launch whose crawl pass the
 // host skipped -- believing the view defers nothing -- it is the only writer, and the host
-// stops skipping when it sees it (vr_host.cpp launch): the next launch of the slot runs the
+// stops skipping when it sees it (vr_launch_plan.h CrawlSkip): the next launch of the slot runs the
 // crawl pass, which drops the stale records and resets the list.  (Rare: one 8-B store.)
 __device__ __forceinline__ void deferral_report(const KView& v) {
     if (v.slot_stat) *reinterpret_cast<uint2*>(v.slot_stat) = uint2{v.launch_id, 1u};
@@ -1936,7 +1936,7 @@ __global__ __launch_bounds__(64 * kCrawlWaves) void crawl_kernel(KScene s, KView
     // (v.crawl_rpw: the host's choice per launch -- 4 for a lone frame, whose time is the
     // longest record's chain; 8 with frames in flight, where the pass's issue cycles count:
     // C5 0.6707 -> 0.6514 ms per frame, profiles/r03/rpw_deep/; 32 since round 6, never slower
-    // and in some runs 4 % faster, vr_host.cpp crawl_rpw_in_flight)
+    // and in some runs 4 % faster, vr_launch_plan.h launch_policy)
     const uint32_t rpw = v.crawl_rpw ? v.crawl_rpw : kCrawlRpw;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, wlane = threadIdx.x & 63u;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
