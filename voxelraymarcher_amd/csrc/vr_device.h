@@ -33,14 +33,14 @@ __device__ __forceinline__ f3 unit(f3 a) {                                      
 __device__ __forceinline__ f3 ld3(const float* p) { return f3{p[0], p[1], p[2]}; }
 
 // Runtime axis select without private-memory arrays.
-__device__ __forceinline__ float comp(f3 v, uint32_t a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
+__host__ __device__ __forceinline__ float comp(f3 v, uint32_t a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
 __device__ __forceinline__ int32_t geti(i3 v, uint32_t a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
 __device__ __forceinline__ void seti(i3& v, uint32_t a, int32_t val) {
     v.x = a == 0 ? val : v.x;
     v.y = a == 1 ? val : v.y;
     v.z = a == 2 ? val : v.z;
 }
-__device__ __forceinline__ void setf(f3& v, uint32_t a, float val) {
+__host__ __device__ __forceinline__ void setf(f3& v, uint32_t a, float val) {
     v.x = a == 0 ? val : v.x;
     v.y = a == 1 ? val : v.y;
     v.z = a == 2 ? val : v.z;
@@ -51,10 +51,19 @@ __device__ __forceinline__ void setf(f3& v, uint32_t a, float val) {
 // NaN -> 0).  v_cvt_i32_f32 / v_cvt_u32_f32 implement exactly that on CDNA;
 // emitting them directly keeps the conversion one branch-free instruction
 // (a C cast is UB out of range and hipcc guards it with control flow).
-__device__ __forceinline__ int32_t f2i(float f) {
+// (f2i also compiles for the host, with the same semantics in plain C++: vr_crawl.h's
+// arithmetic is checked on both sides, tools/crawl_check.hip.)
+__host__ __device__ __forceinline__ int32_t f2i(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
     int32_t r;
     asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(f));
     return r;
+#else
+    if (!(f == f)) return 0;
+    if (f >= 0x1p+31f) return INT32_MAX;
+    if (f <= -0x1p+31f) return INT32_MIN;
+    return (int32_t)f;
+#endif
 }
 __device__ __forceinline__ uint32_t f2u(float f) {
     uint32_t r;
