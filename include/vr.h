@@ -263,7 +263,7 @@ typedef enum {
     VR_SCHEDULE_HEAVIEST_FIRST = 2
 } vr_schedule;
 /* Learned orders (round 5).  Besides the work order, every launch (any schedule) deals the
- * pixels of each 16x16 block to the block's four waves heaviest first (the lane order: a
+ * pixels of each 16x32 block to the block's eight waves heaviest first (the lane order: a
  * wave's lanes then walk about equally far) -- C2 per frame in flight 0.113 -> 0.101 ms.
  * Both are learned from the walk lengths of earlier launches of the SAME view (scene,
  * algorithm, camera, lights, transform, frame size, rows and band / tile deal) on the device
@@ -278,6 +278,19 @@ int vr_forget_orders(int device);
  * pixel renders it as 0; the tile pass reports the deferral and the slot stops skipping, so
  * later launches are exact again).  Never needed by a renderer. */
 int vr_debug_skip_next_crawl(int device);
+/* Test hooks for the lane order.  After vr_debug_capture_lane_order the device's next launch
+ * that makes a lane order (a repeated view) waits for its stream and keeps a host copy of the
+ * order and of the per-pixel walk lengths it was made from.  vr_debug_lane_order returns them:
+ * info = {row length LW, rows, tile-group columns, tile-group rows, block width, block height
+ * (pixels), bytes per entry, seat rule (0 cost order, 1 Morton order)}; pcost (or NULL) takes
+ * info[0] * info[1] words, row-major, (primary walk length << 16 | shadow walk length); perm
+ * (or NULL) takes the order: per block (row-major over ceil(LW / width) x ceil(rows / height)
+ * blocks) width * height entries, entry 64 q + i = row * width + column of the block pixel that
+ * lane i of wave slot q renders (blocks cut by the frame's edge: unspecified).  Call it with
+ * both NULL first for the sizes.  Never needed by a renderer. */
+int vr_debug_capture_lane_order(int device);
+int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t pcost_words, uint8_t* perm,
+                        uint64_t perm_bytes);
 /* Every vr_render* call returns VR_E_INVALID on a stream that is capturing a HIP graph
  * (its per-device slot ring and work-order bookkeeping are host state that a graph replay
  * would not repeat). */

@@ -137,7 +137,7 @@ struct KView {
     // loop iterations) to cost[tile * kWavesPerTileGroup + wave], tile = row * columns + column.
     const uint32_t* order;
     uint32_t* cost;
-    // Lane order (round 5, vr_march.hip lane_pixel): per pixel block (16x16 by default) the slot
+    // Lane order (round 5, vr_march.hip lane_pixel): per pixel block (16x32 by default) the slot
     // of each pixel, dealing them to the block's waves heaviest first (or null: 8x8 tiles;
     // vr::perm_bytes(gx, gy) bytes); pcost (or null): each lane
     // writes its pixel's walk lengths at [l * LW + x] (primary << 16 | shadow, each saturated at
@@ -207,10 +207,16 @@ constexpr uint32_t kWavesPerTileGroup = 2;
 // Heaviest-first work order of a grid of `columns` x `n / columns` workgroups from the
 // costs a launch wrote (KView::cost): one workgroup, a counting sort by cost.
 hipError_t launch_order(const uint32_t* cost, uint32_t n, uint32_t columns, uint32_t* order, hipStream_t stream);
-// The lane orders of a grid of gx x gy tile groups (gx x ceil(gy / 2) 16x16 blocks) from the
+// The lane orders of a grid of gx x gy tile groups (gx x ceil(gy / 4) 16x32 blocks by default) from the
 // per-pixel walk lengths a launch wrote (KView::pcost, rows x LW words); with cost non-null
 // also the waves' walk lengths under the new lane order (KView::cost's layout).
 size_t perm_bytes(uint32_t gx, uint32_t gy);   // the lane order of a gx x gy grid
+// How the build lays a lane order out: the block's sides in pixels, the bytes of one perm
+// entry and the seat rule (vr_march.hip VR_LANE_SEAT) -- for vr_debug_lane_order's readers.
+struct LaneShape {
+    uint32_t block_x, block_y, entry_bytes, seat;
+};
+LaneShape lane_shape();
 hipError_t launch_perm(const uint32_t* pcost, uint32_t LW, uint32_t rows, uint32_t gx, uint32_t gy, uint8_t* perm,
                        uint32_t* cost, hipStream_t stream);
 

@@ -139,6 +139,14 @@ struct SlotRing {
         uint32_t last_idx = 0;
         uint64_t last_key = 0;             // the view of the device's previous launch
         bool force_skip = false;           // vr_debug_skip_next_crawl (tests)
+        // vr_debug_capture_lane_order (tests): the next lane order made on the device is kept
+        // here with the walk lengths it was made from, for vr_debug_lane_order
+        bool capture_lane = false;
+        struct LaneCapture {
+            uint32_t LW = 0, rows = 0, gx = 0, gy = 0;
+            std::vector<uint32_t> pcost;
+            std::vector<uint8_t> perm;
+        } lane_capture;
         // No other stream's launch is running on the device.  (The lock orders launches:
         // "previous" is well defined.  The event is queried only when there is a previous
         // launch and it was on another stream: this is on the enqueue path.)
@@ -311,7 +319,7 @@ hipError_t bind_work_order(vr::WorkOrder& W, uint32_t gx, uint32_t gy, uint64_t 
 
 // The lane order, kept like the work order but for every schedule: this slot's if it was
 // made for this view (v.perm), made from this launch's per-pixel walk lengths (v.pcost;
-// `relane`) when missing and the view repeats.  It permutes pixels within 16x16 blocks
+// `relane`) when missing and the view repeats.  It permutes pixels within lane blocks (16x32)
 // only: any permutation renders the same pixels.  On an error `what` names the step.
 hipError_t bind_lane_order(vr::LaneOrder& L, uint32_t gx, uint32_t gy, uint64_t key, bool repeat, hipStream_t st,
                            vr::KView& v, bool& relane, const char*& what) {
@@ -329,7 +337,7 @@ hipError_t bind_lane_order(vr::LaneOrder& L, uint32_t gx, uint32_t gy, uint64_t 
     relane = vr::remake_due(match, false, repeat, L.age, order_refresh());
     if (!relane) return hipSuccess;
     // 4 B per pixel, only between this launch's tile pass and its perm_kernel (freed
-    // stream-ordered after it): the slots keep 1 B per pixel each, not 5
+    // stream-ordered after it): the slots keep 2 B per pixel each, not 6
     what = "lane order walk lengths";
     return hipMallocAsync((void**)&v.pcost, sizeof(uint32_t) * (size_t)v.LW * v.local_rows, st);
 }
@@ -466,6 +474,16 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
         e = vr::launch_perm(v.pcost, v.LW, v.local_rows, gx, gy, S.lane.perm, with_costs ? S.work.cost : nullptr, st);
         S.lane.learned(gx, gy, key, e == hipSuccess);
         S.work.relaned = !with_costs;
+        if (e == hipSuccess && D.capture_lane) {     // (tests only: waits for the stream)
+            D.capture_lane = false;
+            SlotRing::Dev::LaneCapture& C = D.lane_capture;
+            C.LW = v.LW, C.rows = v.local_rows, C.gx = gx, C.gy = gy;
+            C.pcost.resize((size_t)v.LW * v.local_rows);
+            C.perm.resize(vr::perm_bytes(gx, gy));
+            e = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = hipMemcpy(C.pcost.data(), v.pcost, sizeof(uint32_t) * C.pcost.size(), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(C.perm.data(), S.lane.perm, C.perm.size(), hipMemcpyDeviceToHost);
+        }
     }
     if (e == hipSuccess && (remake || with_costs)) {
         // (on a side stream instead -- one more stream than the box's 4 hardware queues
@@ -604,6 +622,37 @@ int vr_debug_skip_next_crawl(int device) {
     SlotRing::Dev& D = g_defer_ring.dev[device];
     std::lock_guard<std::mutex> lk(D.mu);
     D.force_skip = true;
+    return VR_OK;
+}
+
+int vr_debug_capture_lane_order(int device) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    D.capture_lane = true;
+    D.lane_capture = {};
+    return VR_OK;
+}
+
+int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t pcost_words, uint8_t* perm,
+                        uint64_t perm_bytes) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    if (!info) return fail(VR_E_INVALID, "info is NULL");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    const SlotRing::Dev::LaneCapture& C = D.lane_capture;
+    if (C.perm.empty()) return fail(VR_E_INVALID, "no lane order captured (vr_debug_capture_lane_order, then a repeated view)");
+    const vr::LaneShape sh = vr::lane_shape();
+    const uint32_t words[8] = {C.LW, C.rows, C.gx, C.gy, sh.block_x, sh.block_y, sh.entry_bytes, sh.seat};
+    std::memcpy(info, words, sizeof words);
+    if (pcost) {
+        if (pcost_words != C.pcost.size()) return fail(VR_E_INVALID, "pcost_words is not info[0] * info[1]");
+        std::memcpy(pcost, C.pcost.data(), sizeof(uint32_t) * C.pcost.size());
+    }
+    if (perm) {
+        if (perm_bytes != C.perm.size()) return fail(VR_E_INVALID, "perm_bytes is not the captured order's size");
+        std::memcpy(perm, C.perm.data(), C.perm.size());
+    }
     return VR_OK;
 }
 

@@ -75,7 +75,7 @@ struct WorkOrder : Learned {
     void learned(uint32_t x, uint32_t y, uint64_t k, bool ok) { Learned::learned(x, y, k, ok); relaned = false; }
     void forget() { valid = relaned = false; }
 };
-// Per slot: the lane order (vr_march.hip lane_pixel): per 16x16 block its pixels heaviest first.
+// Per slot: the lane order (vr_march.hip lane_pixel): per lane block (16x32 pixels) its pixels heaviest first.
 struct LaneOrder : Learned {
     uint8_t* perm = nullptr;       // vr::perm_bytes(gx, gy)
     size_t bcap = 0;

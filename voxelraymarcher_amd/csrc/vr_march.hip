@@ -129,22 +129,51 @@ __device__ __forceinline__ void tile_group(const KView& v, uint32_t& bx, uint32_
 
 // The pixel (local column x, local row l) of this tile-pass lane.  Without a lane order
 // (KView::perm null) wave w of tile group (bx, by) is the 8x8 tile (2 bx + w, by).  With one,
-// the tile groups of a kLaneBlock x kLaneBlock pixel block share its pixels: they are dealt
+// the tile groups of a kLaneBlockX x kLaneBlockY pixel block share its pixels: they are dealt
 // to the block's waves heaviest first (perm_kernel, from the walk lengths an earlier launch
 // of the view recorded), so a wave's lanes walk about equally far and finish together --
-// 16x16 blocks, C2: 24 % fewer wave-iterations for the same per-lane work (the oracle's
-// per-pixel counts, profiles/r05/lane_sort_sim.py, lane_order/).  Slot q of a block is wave
+// C2: 25 % fewer wave-iterations for the same per-lane work with 16x16 blocks, 32 % with
+// 16x32 (the oracle's per-pixel counts, profiles/r05/lane_sort_sim.py).  Slot q of a block is wave
 // w of its tile group (bx mod kLbX, by mod kLbY) in row-major order, q = 2 (tile group) + w;
-// lane i of slot q renders pixel perm[block * kLanePixels + 64 q + i] = (row * kLaneBlock +
+// lane i of slot q renders pixel perm[block * kLanePixels + 64 q + i] = (row * kLaneBlockX +
 // column) of the block.  Blocks cut by the grid's edge keep the 8x8 tiles.
-#ifndef VR_LANE_BLOCK
-#define VR_LANE_BLOCK 16
+// The block is kLaneBlockX x kLaneBlockY pixels, 16 wide and 32 high by default (8 wave
+// slots, 2-byte perm entries): VR_LANE_BLOCK=16|32 sets both sides, VR_LANE_BLOCK_X /
+// VR_LANE_BLOCK_Y one each.  Measured per frame in flight, either seat rule
+// (profiles/lane_seat/): C2 16x16 0.0975 ms, 32x16 0.104, 32x32 0.0957, 16x32 0.0950; 16x32 is
+// also the fastest on C3 (0.1843 -> 0.1798), C4 (0.0473 -> 0.0458; 32x32: 0.0490) and C5.  A
+// launch alone with both orders learned is slower with it (C2 0.1096 -> 0.1220 ms; 32x32
+// 0.127): larger blocks make fewer, fuller waves, which pays when frames overlap.
+#ifdef VR_LANE_BLOCK
+#define VR_LANE_BLOCK_DEFAULT_X VR_LANE_BLOCK
+#define VR_LANE_BLOCK_DEFAULT_Y VR_LANE_BLOCK
+#else
+#define VR_LANE_BLOCK_DEFAULT_X 16
+#define VR_LANE_BLOCK_DEFAULT_Y 32
 #endif
-constexpr uint32_t kLaneBlock = VR_LANE_BLOCK;
-static_assert(kLaneBlock == 16 || kLaneBlock == 32, "lane block: 16 or 32 pixels");
-constexpr uint32_t kLanePixels = kLaneBlock * kLaneBlock;
-constexpr uint32_t kLbX = kLaneBlock / (8u * kTilesX), kLbY = kLaneBlock / (8u * kTilesY);
-using PermT = std::conditional<kLaneBlock == 16, uint8_t, uint16_t>::type;
+#ifndef VR_LANE_BLOCK_X
+#define VR_LANE_BLOCK_X VR_LANE_BLOCK_DEFAULT_X
+#endif
+#ifndef VR_LANE_BLOCK_Y
+#define VR_LANE_BLOCK_Y VR_LANE_BLOCK_DEFAULT_Y
+#endif
+constexpr uint32_t kLaneBlockX = VR_LANE_BLOCK_X, kLaneBlockY = VR_LANE_BLOCK_Y;
+static_assert((kLaneBlockX == 16 || kLaneBlockX == 32) && (kLaneBlockY == 16 || kLaneBlockY == 32),
+              "lane block: 16 or 32 pixels a side");
+constexpr uint32_t kLanePixels = kLaneBlockX * kLaneBlockY;
+constexpr uint32_t kLbX = kLaneBlockX / (8u * kTilesX), kLbY = kLaneBlockY / (8u * kTilesY);
+using PermT = std::conditional<kLanePixels == 256, uint8_t, uint16_t>::type;
+// The seat of a pixel within its wave slot (which lane renders it; the slot's 64 pixels are
+// the same either way): 0 = by cost rank, as perm_kernel's sort leaves them, 1 = in ascending
+// Morton order of (column, row) in the block, so that neighbouring lanes, lane quads and
+// 16-lane groups cover compact patches of the block.  Morton seats measured no faster and
+// moved no vector-L1 counter (C2 per frame in flight 0.0976 -> 0.0974 ms, inside the run-to-run
+// spread; TCP tag accesses per launch 1.570e7 -> 1.580e7, profiles/lane_seat/), so 0 stays.
+#ifndef VR_LANE_SEAT
+#define VR_LANE_SEAT 0
+#endif
+constexpr uint32_t kLaneSeat = VR_LANE_SEAT;
+static_assert(kLaneSeat <= 1u, "lane seat: 0 (cost order) or 1 (Morton order)");
 constexpr bool kLaneOrder = kTilesX == 2 && kTilesY == 1;   // (other tile shapes ignore perm)
 __device__ __forceinline__ void lane_pixel(const KView& v, uint32_t& x, uint32_t& l) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -155,8 +184,8 @@ __device__ __forceinline__ void lane_pixel(const KView& v, uint32_t& x, uint32_t
         const uint32_t q = ((by % kLbY) * kLbX + bx % kLbX) * kTilesX + wave;
         const uint32_t blk = BY * ((gridDim.x + kLbX - 1u) / kLbX) + BX;
         const uint32_t p = reinterpret_cast<const PermT*>(v.perm)[(size_t)blk * kLanePixels + q * 64u + lane];
-        x = BX * kLaneBlock + p % kLaneBlock;
-        l = BY * kLaneBlock + p / kLaneBlock;
+        x = BX * kLaneBlockX + p % kLaneBlockX;
+        l = BY * kLaneBlockY + p / kLaneBlockX;
     } else {
         x = (bx * kTilesX + wave % kTilesX) * 8u + (lane & 7u);
         l = (by * kTilesY + wave / kTilesX) * 8u + (lane >> 3);
@@ -1616,11 +1645,37 @@ __global__ __launch_bounds__(64 * kTilesX * kTilesY, (TileWaves<ALGO, HI>::value
 // lane order -- KView::cost's layout; max(primary) + max(shadow) over the wave's pixels, what
 // the wave runs; blocks cut by the grid's edge keep the 8x8 tiles and write each tile's -- so
 // the work order made from them next matches the lane order.
-constexpr uint32_t kLaneShift = kLaneBlock == 16 ? 8u : 10u;
+// With kLaneSeat == 1 each wave then sorts the 64 pixels of its own slot once more, by the
+// Morton code of (column, row) ascending (lane_morton): the slot's pixel set, and with it
+// wmax and cost, is what the cost ranks made it; only the lanes within the slot change.
+constexpr uint32_t kLaneShift = kLanePixels == 256 ? 8u : kLanePixels == 512 ? 9u : 10u;
+// A wave's 64 keys sorted by a bitonic network of lane shuffles: lane i gets the i-th largest
+// (DESCENDING) or the i-th smallest.
+template <bool DESCENDING>
+__device__ __forceinline__ uint32_t wave_sort(uint32_t key, uint32_t lane) {
+    for (uint32_t size = 2; size <= 64u; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)key, (int)stride, 64);
+            const bool keep_max = (((lane & stride) == 0u) == ((lane & size) == 0u)) == DESCENDING;
+            key = keep_max ? max(key, other) : min(key, other);
+        }
+    }
+    return key;
+}
+// The Morton code of block pixel (px, py): bit 2i is bit i of the column, bit 2i + 1 bit i of
+// the row, for the low four bits of each; a fifth bit of the column (32 wide) is bit 8, of the
+// row (32 high) bit 9.
+__device__ __forceinline__ uint32_t lane_morton(uint32_t px, uint32_t py) {
+    auto spread4 = [](uint32_t v) {
+        v = (v | v << 2) & 0x33u;
+        return (v | v << 1) & 0x55u;
+    };
+    return spread4(px & 15u) | spread4(py & 15u) << 1 | (px >> 4) << 8 | (py >> 4) << 9;
+}
 __global__ __launch_bounds__(kLanePixels) void perm_kernel(const uint32_t* __restrict__ pcost, uint32_t LW,
                                                            uint32_t rows, uint32_t gx, uint32_t gy,
                                                            uint8_t* __restrict__ perm, uint32_t* __restrict__ cost) {
-    constexpr uint32_t kWaves = kLanePixels / 64u, kTiles = (kLaneBlock / 8u) * (kLaneBlock / 8u);
+    constexpr uint32_t kWaves = kLanePixels / 64u, kTiles = (kLaneBlockX / 8u) * (kLaneBlockY / 8u);
     __shared__ uint32_t sorted[kLanePixels];
     __shared__ __attribute__((aligned(16))) PermT slots[kLanePixels];
     __shared__ uint32_t wmax[2u * kWaves];   // per wave slot (or 8x8 tile): max primary, max shadow
@@ -1628,8 +1683,8 @@ __global__ __launch_bounds__(kLanePixels) void perm_kernel(const uint32_t* __res
     static_assert(kTiles == kWaves, "one 8x8 tile per wave slot");
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const uint32_t nbx = (gx + kLbX - 1u) / kLbX, BX = blockIdx.x % nbx, BY = blockIdx.x / nbx;
-    const uint32_t px = t % kLaneBlock, py = t / kLaneBlock;
-    const uint32_t x = BX * kLaneBlock + px, l = BY * kLaneBlock + py;
+    const uint32_t px = t % kLaneBlockX, py = t / kLaneBlockX;
+    const uint32_t x = BX * kLaneBlockX + px, l = BY * kLaneBlockY + py;
     // a pixel's weight: a wave runs its primary walks until the slowest ends, then its shadow
     // walks, so it costs max(primary) + max(shadow) over its lanes; max(p, s) + (p + s) / 8
     // groups lanes best of the weights tried on the oracle's C2 counts (1.4 % fewer
@@ -1648,12 +1703,12 @@ __global__ __launch_bounds__(kLanePixels) void perm_kernel(const uint32_t* __res
     if ((BX + 1u) * kLbX > gx || (BY + 1u) * kLbY > gy) {
         if (cost) {                 // the block's 8x8 tiles that exist
             __syncthreads();
-            const uint32_t ti = (py >> 3) * (kLaneBlock / 8u) + (px >> 3);
+            const uint32_t ti = (py >> 3) * (kLaneBlockX / 8u) + (px >> 3);
             atomicMax(&wmax[ti], p);
             atomicMax(&wmax[kWaves + ti], s);
             __syncthreads();
             if (t < kTiles) {
-                const uint32_t tx = t % (kLaneBlock / 8u), ty = t / (kLaneBlock / 8u);
+                const uint32_t tx = t % (kLaneBlockX / 8u), ty = t / (kLaneBlockX / 8u);
                 const uint32_t col = BX * kLbX + tx / kTilesX, row = BY * kLbY + ty;
                 if (col < gx && row < gy)
                     cost[(row * gx + col) * kWavesPerTileGroup + tx % kTilesX] = wmax[t] + wmax[kWaves + t];
@@ -1661,14 +1716,7 @@ __global__ __launch_bounds__(kLanePixels) void perm_kernel(const uint32_t* __res
         }
         return;
     }
-    uint32_t key = (c << kLaneShift) | t;
-    for (uint32_t size = 2; size <= 64u; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            const uint32_t other = (uint32_t)__shfl_xor((int)key, (int)stride, 64);
-            const bool keep_max = ((lane & stride) == 0u) == ((lane & size) == 0u);
-            key = keep_max ? max(key, other) : min(key, other);
-        }
-    }
+    const uint32_t key = wave_sort<true>((c << kLaneShift) | t, lane);
     sorted[t] = key;                // lane i of wave w: the wave's i-th largest key
     __syncthreads();
     uint32_t rank = lane;
@@ -1693,6 +1741,12 @@ __global__ __launch_bounds__(kLanePixels) void perm_kernel(const uint32_t* __res
         const uint32_t g = t / kTilesX;
         const uint32_t col = BX * kLbX + g % kLbX, row = BY * kLbY + g / kLbX;
         cost[(row * gx + col) * kWavesPerTileGroup + t % kTilesX] = wmax[t] + wmax[kWaves + t];
+    }
+    if (kLaneSeat == 1u) {          // this wave's threads hold the 64 seats of slot `wave`
+        const uint32_t q = slots[t];
+        const uint32_t k = wave_sort<false>(lane_morton(q % kLaneBlockX, q / kLaneBlockX) << kLaneShift | q, lane);
+        slots[t] = (PermT)(k & (kLanePixels - 1u));
+        __syncthreads();
     }
     constexpr uint32_t kWords = kLanePixels * sizeof(PermT) / 4u;
     uint32_t* out = reinterpret_cast<uint32_t*>(perm + (size_t)blockIdx.x * kLanePixels * sizeof(PermT));
@@ -1945,6 +1999,10 @@ void march_grid(const KView& v, uint32_t& columns, uint32_t& rows) {
 
 size_t perm_bytes(uint32_t gx, uint32_t gy) {
     return (size_t)((gx + kLbX - 1u) / kLbX) * ((gy + kLbY - 1u) / kLbY) * kLanePixels * sizeof(PermT);
+}
+
+LaneShape lane_shape() {
+    return {kLaneBlockX, kLaneBlockY, (uint32_t)sizeof(PermT), kLaneSeat};
 }
 
 hipError_t launch_perm(const uint32_t* pcost, uint32_t LW, uint32_t rows, uint32_t gx, uint32_t gy, uint8_t* perm,

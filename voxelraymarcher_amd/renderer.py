@@ -434,6 +434,30 @@ def debug_skip_next_crawl(device: int = 0) -> None:
     check(lib().vr_debug_skip_next_crawl(int(device)), "vr_debug_skip_next_crawl")
 
 
+def debug_capture_lane_order(device: int = 0) -> None:
+    """Test hook (vr_debug_capture_lane_order): the device's next launch that makes a lane order
+    keeps a host copy of it and of the walk lengths it was made from."""
+    check(lib().vr_debug_capture_lane_order(int(device)), "vr_debug_capture_lane_order")
+
+
+def debug_lane_order(device: int = 0):
+    """Test hook (vr_debug_lane_order): the captured lane order as (info, pcost, perm) -- info
+    a dict (LW, rows, gx, gy, block_x, block_y, entry_bytes, seat), pcost a (rows, LW) uint32
+    array (primary << 16 | shadow walk lengths), perm a (blocks, block_x * block_y) array of
+    block pixels (row * block_x + column), entry 64 q + i the pixel of lane i of wave slot q."""
+    import numpy as np
+    raw = (ctypes.c_uint32 * 8)()
+    check(lib().vr_debug_lane_order(int(device), raw, None, 0, None, 0), "vr_debug_lane_order")
+    info = dict(zip(("LW", "rows", "gx", "gy", "block_x", "block_y", "entry_bytes", "seat"), (int(x) for x in raw)))
+    n = info["block_x"] * info["block_y"]
+    blocks = -(-info["LW"] // info["block_x"]) * (-(-info["rows"] // info["block_y"]))
+    pcost = np.empty((info["rows"], info["LW"]), dtype=np.uint32)
+    perm = np.empty((blocks, n), dtype=np.uint8 if info["entry_bytes"] == 1 else np.uint16)
+    check(lib().vr_debug_lane_order(int(device), raw, c_void_p(pcost.ctypes.data), pcost.size,
+                                    c_void_p(perm.ctypes.data), perm.nbytes), "vr_debug_lane_order")
+    return info, pcost, perm
+
+
 def render_tiles(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, lighting: _capi.VrLighting,
                  info: VoxelSceneInfo, width: int, height: int, band_rows: int, tile_cols: int, rank: int,
                  nranks: int, out: torch.Tensor, stream=None) -> torch.Tensor:
