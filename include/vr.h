@@ -56,7 +56,7 @@ typedef struct {
     int32_t use_shadows;
 } vr_lighting;
 
-/* Immutable per-device scene: region table + VCS or cuckoo storage images.
+/* Per-device scene (changed only by vr_scene_edit): region table + VCS or cuckoo storage images.
  * Replaces VoxelSceneCPU::generateVoxelScene's device pointer table
  * (geometry/VoxelSceneCPU.cuh:49-93) plus the device-side virtual adapters
  * built by the generateVoxelScene kernel (renderer/Renderer.cuh:1066-1086). */
@@ -127,6 +127,53 @@ int vr_scene_load_vox(int device, vr_store store, const char* path, vr_scene** o
 
 int vr_scene_get_info(const vr_scene* s, vr_scene_info* out);
 void vr_scene_destroy(vr_scene* s);
+
+/* As an edit's colour: delete the voxel. */
+#define VR_VOXEL_REMOVE 0xFFFFFFFFu
+
+/* Edit a scene in place: VoxelSceneCPU::insertVoxel (VoxelSceneCPU.cuh:16-46) for a batch,
+ * plus removal, without building the scene again.  Applies n edits in order: edit i sets
+ * voxel xyz[3i..3i+2] (world voxel coordinates) to colour rgb[i] (< 2^24: inserts or
+ * overwrites) or, with rgb[i] == VR_VOXEL_REMOVE, deletes it (absent: no-op).  Later edits
+ * of a coordinate win over earlier ones.  inputs_on_device != 0: xyz/rgb are buffers on the
+ * scene's device.
+ *
+ * The scene keeps its grid frame (diameter, min_coord).  Afterwards the five buffers of
+ * vr_scene_digest are byte for byte what vr_scene_create over the edited voxel set
+ * produces whenever that build has the same frame (regions born or emptied, clusters that
+ * appear or vanish, value indices, table sizes, bases and the cuckoo placement included);
+ * vr_scene_get_info reports the new voxel_count, region_count and device_bytes.
+ *
+ * All or nothing -- the scene is left exactly as it was when the call fails:
+ *   VR_E_INVALID  s NULL; xyz or rgb NULL with n > 0; a colour >= 2^24 other than
+ *                 VR_VOXEL_REMOVE, or a voxel whose 64^3 region lies outside the frame (the
+ *                 message names the first such index; growing the frame needs
+ *                 vr_scene_create); a VCS scene that would pass 65536 occupied regions; a
+ *                 stream that is capturing a HIP graph
+ *   VR_E_BUILD    a cuckoo region that cannot be built
+ * n == 0 returns VR_OK and does nothing.
+ *
+ * Ordering: the work runs on `stream` (NULL = the null stream) and the call returns when
+ * the edited scene is ready, as vr_scene_create_ex does.  Renders of this scene queued
+ * earlier on `stream` see the old scene; the old buffers are released only after they
+ * have finished.  The caller must have NO render of this scene in flight on another
+ * stream, and must not call vr_scene_edit, vr_scene_voxels or vr_render* on this scene
+ * from another thread meanwhile. */
+int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n,
+                  int inputs_on_device, void* stream);
+
+/* The scene's voxels (after duplicate resolution): the inverse of vr_scene_create, e.g. to
+ * save an edited scene with vr_vxb_write.  Each stored voxel once, ordered by ascending
+ * region index (x + y * diameter + z * diameter^2 of its region in the frame), then in the
+ * store's key order inside a region: the hash table's by x<<20 | y<<10 | z of the local
+ * coordinates, the cluster store's by cluster id (x>>3)<<6 | (y>>3)<<3 | z>>3, then by
+ * (x&7)<<6 | (y&7)<<3 | z&7.  Two-call protocol like vr_vox_read: with xyz == NULL only
+ * counts (*n_out); otherwise writes voxel_count voxels (3 int32 world coordinates + 1
+ * colour each) and sets *n_out; a capacity below the count returns VR_E_INVALID with
+ * *n_out set.  outputs_on_device != 0: xyz/rgb are buffers on the scene's device.  Runs on
+ * `stream` and returns when the arrays are written. */
+int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capacity,
+                    int outputs_on_device, void* stream, size_t* n_out);
 
 /* rayMarchSceneOriginal / rayMarchSceneJumpAxis (Renderer.cuh:1033-1063) as
  * launched by runRaymarchingKernel (Main.cu:105-163), for image rows

@@ -84,6 +84,8 @@ SIGNATURES = {
     "vr_scene_load_vox": (c_int, [c_int, c_int, c_char_p, POINTER(c_void_p)]),
     "vr_scene_get_info": (c_int, [c_void_p, POINTER(VrSceneInfo)]),
     "vr_scene_destroy": (None, [c_void_p]),
+    "vr_scene_edit": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "vr_scene_voxels": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_size_t)]),
     "vr_render": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float), c_uint32,
                           c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
     "vr_render_bands": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float),

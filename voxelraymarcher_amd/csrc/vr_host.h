@@ -51,6 +51,9 @@ struct vr_scene {
     // scene's address), drawn by vr_scene.cpp
     const uint64_t serial;
     explicit vr_scene(uint64_t id) : serial(id) {}
+    // bumped by every successful non-empty vr_scene_edit: with `serial`, the identity of the
+    // scene's CONTENT (which pixels a view defers depends on it; vr_launch.cpp view_key)
+    uint64_t revision = 0;
     int device = 0;
     vr_store store = VR_STORE_VCS;
     uint32_t D = 1;

@@ -41,7 +41,7 @@ constexpr uint32_t kVcsMaxRegions = 65536u;
 // words of a cuckoo region's key-presence filter (64^3 bits)
 constexpr uint32_t kHashFilterWords = 8192u;
 
-// Device view of one immutable scene.  All offsets are 32-bit word indices.
+// Device view of one scene (vr_scene_edit replaces its buffers as a set).  Offsets are 32-bit word indices.
 //  region_slot[D^3]          : region index r, or kNone (null StorageStructure*)
 //  VCS   : vcs_mask[r*8192 + slot*16 + w]  (one 128-B record per cluster of an
 //                              occupied region; VoxelClusterStore::deviceBlockMemAddress

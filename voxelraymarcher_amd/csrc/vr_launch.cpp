@@ -244,7 +244,8 @@ struct SlotLease {
 };
 
 // The view a launch renders, for the learned orders and the crawl-pass skip: an FNV-1a hash
-// of the scene (its per-process serial), the algorithm and every value field of the view --
+// of the scene (its per-process serial and its revision, which every vr_scene_edit that
+// changes it bumps: an edit changes which pixels defer), the algorithm and every value field of the view --
 // the KView prefix above `out`: camera (llc, hor, ver, org), lights (L, LC, LP and the
 // host-made Lr, L_fast, Lw, L_order, L_cls, L_unit, L_eq), transform (translation, scale_f),
 // use_point_light, use_shadows, frame size (W, H), the launch's rows (row0, band_rows, rank,
@@ -256,6 +257,7 @@ struct SlotLease {
 uint64_t view_key(const vr_scene* s, vr_algo algo, const vr::KView& v) {
     const uint32_t a = (uint32_t)algo;
     uint64_t h = vr::fnv1a(vr::kFnvBasis, &s->serial, sizeof s->serial);
+    h = vr::fnv1a(h, &s->revision, sizeof s->revision);
     h = vr::fnv1a(h, &a, sizeof a);
     return vr::fnv1a(h, &v, offsetof(vr::KView, out));
 }

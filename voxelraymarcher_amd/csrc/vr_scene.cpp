@@ -342,6 +342,12 @@ int add_derived_bits(vr_scene* s, hipStream_t stream) {
     return VR_OK;
 }
 
+// The scene as vr_edit.hip's kernels read it.
+vr::GpuImage gpu_image(const vr_scene* s) {
+    return vr::GpuImage{(int)s->store, s->D, s->min_coord, s->n_regions, s->n_voxels, s->region_slot.p, s->vcs_mask.p,
+                        s->vcs_vals.p, s->ht_meta.p, s->ht_slots.p, s->ht_filter.p};
+}
+
 int build_scene_raw(int device, vr_store store, const int32_t* xyz, const uint32_t* rgb, size_t n, bool on_device,
                     vr_build mode, void* stream, vr_scene** out) {
     if (!out) return fail(VR_E_INVALID, "out is NULL");
@@ -448,6 +454,100 @@ int vr_scene_get_info(const vr_scene* s, vr_scene_info* out) {
     out->voxel_count = s->n_voxels;
     out->device_bytes = s->device_bytes();
     out->device = s->device;
+    return VR_OK;
+}
+
+int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n, int inputs_on_device, void* stream) {
+    if (!s) return fail(VR_E_INVALID, "vr_scene_edit: scene is NULL");
+    if (n && (!xyz || !rgb)) return fail(VR_E_INVALID, "vr_scene_edit: xyz/rgb NULL");
+    if (n == 0) return VR_OK;
+    if (n >= 0xFFFFFFFFull) return fail(VR_E_INVALID, "vr_scene_edit: too many edits");
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(VR_E_INVALID, "vr_scene_edit cannot be captured into a HIP graph (stream is capturing)");
+    const int32_t* dxyz = xyz;
+    const uint32_t* drgb = rgb;
+    void *tx = nullptr, *tc = nullptr;
+    auto release = [&]() {
+        if (tx) (void)hipFree(tx);
+        if (tc) (void)hipFree(tc);
+    };
+    if (!inputs_on_device) {
+        e = hipMalloc(&tx, 3 * n * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(&tc, n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(tx, xyz, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(tc, rgb, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { release(); return hip_fail(e, "edit upload"); }
+        dxyz = (const int32_t*)tx;
+        drgb = (const uint32_t*)tc;
+    }
+    vr::GpuScene g;
+    std::string err;
+    const int rc = vr::edit_scene_gpu(gpu_image(s), dxyz, drgb, n, st, g, err);
+    release();
+    // the new image as a scene of its own: freed whole if anything fails, swapped in otherwise
+    ScenePtr t = new_scene(s->device, s->store);
+    t->D = g.D; t->min_coord = g.min_coord;
+    t->n_regions = g.n_regions; t->n_voxels = g.n_voxels;
+    t->region_slot = DevBuf{g.region_slot, g.region_slot_bytes};
+    t->vcs_mask = DevBuf{g.vcs_mask, g.vcs_mask_bytes};
+    t->vcs_vals = DevBuf{g.vcs_vals, g.vcs_vals_bytes};
+    t->ht_meta = DevBuf{g.ht_meta, g.ht_meta_bytes};
+    t->ht_slots = DevBuf{g.ht_slots, g.ht_slots_bytes};
+    if (rc) return fail(rc == -1 ? VR_E_INVALID : rc == -5 ? VR_E_BUILD : VR_E_HIP, "scene edit: " + err);
+    if (const int rd = add_derived_bits(t.get(), st)) return rd;
+    // the stream has drained (add_derived_bits): renders queued on it before the edit are done
+    std::swap(s->n_regions, t->n_regions);
+    std::swap(s->n_voxels, t->n_voxels);
+    DevBuf vr_scene::*bufs[] = {&vr_scene::region_slot, &vr_scene::vcs_mask, &vr_scene::vcs_vals, &vr_scene::ht_meta,
+                                &vr_scene::ht_slots, &vr_scene::vcs_cbits, &vr_scene::ht_filter};
+    for (auto b : bufs) std::swap(s->*b, (*t).*b);
+    ++s->revision;
+    return VR_OK;   // t, now the old image, is freed here
+}
+
+int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capacity, int outputs_on_device, void* stream,
+                    size_t* n_out) {
+    if (!s || !n_out) return fail(VR_E_INVALID, "vr_scene_voxels: NULL argument");
+    const size_t m = (size_t)s->n_voxels;
+    *n_out = m;
+    if (!xyz) return VR_OK;
+    if (!rgb) return fail(VR_E_INVALID, "vr_scene_voxels: rgb NULL");
+    if (capacity < m)
+        return fail(VR_E_INVALID, "vr_scene_voxels: capacity " + std::to_string(capacity) + " below the scene's " +
+                                      std::to_string(m) + " voxels");
+    if (m == 0) return VR_OK;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    int32_t* dxyz = xyz;
+    uint32_t* drgb = rgb;
+    void *tx = nullptr, *tc = nullptr;
+    auto release = [&]() {
+        if (tx) (void)hipFree(tx);
+        if (tc) (void)hipFree(tc);
+    };
+    hipError_t e = hipSuccess;
+    if (!outputs_on_device) {
+        e = hipMalloc(&tx, 3 * m * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(&tc, m * sizeof(uint32_t));
+        if (e != hipSuccess) { release(); return hip_fail(e, "voxel export buffers"); }
+        dxyz = (int32_t*)tx;
+        drgb = (uint32_t*)tc;
+    }
+    std::string err;
+    const int rc = vr::export_scene_gpu(gpu_image(s), dxyz, drgb, st, err);
+    if (rc == 0 && !outputs_on_device) {
+        e = hipMemcpyAsync(xyz, tx, 3 * m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(rgb, tc, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    release();
+    if (rc) return fail(rc == -1 ? VR_E_INVALID : VR_E_HIP, "scene export: " + err);
+    if (e != hipSuccess) return hip_fail(e, "voxel download");
     return VR_OK;
 }
 

@@ -91,8 +91,11 @@ class VoxelSceneInfo:
     scale: int = 1
 
 
+VOXEL_REMOVE = 0xFFFFFFFF   # VR_VOXEL_REMOVE: as an edit's colour, delete the voxel
+
+
 class DeviceScene:
-    """One immutable scene resident in HBM (owns the vr_scene handle)."""
+    """One scene resident in HBM (owns the vr_scene handle); changed only by edit()."""
 
     def __init__(self, handle: c_void_p):
         self._h = handle
@@ -115,6 +118,53 @@ class DeviceScene:
         d = (ctypes.c_uint64 * 5)()
         check(lib().vr_scene_digest(self.handle, d), "vr_scene_digest")
         return tuple(int(x) for x in d)
+
+    def edit(self, xyz, rgb, stream=None) -> None:
+        """vr_scene_edit: apply the edits in order, in place.  Edit i sets voxel xyz[i] to
+        colour rgb[i] (< 2^24) or, with VOXEL_REMOVE, deletes it; later edits of a coordinate
+        win.  xyz/rgb: numpy arrays, or torch tensors on the scene's device.  All or nothing
+        (VrError leaves the scene as it was); runs on `stream` (default: the current stream)
+        and returns when the scene is ready.  With several GPUs every rank holds its own
+        scene: the same batch applied on every rank gives identical images."""
+        sp = _stream_ptr(stream)
+        if hasattr(xyz, "is_cuda") and xyz.is_cuda:
+            xyz = xyz.to(torch.int32).contiguous().reshape(-1, 3)
+            rgb = rgb.contiguous().reshape(-1)
+            if rgb.dtype not in (torch.int32, torch.uint32):
+                # (VOXEL_REMOVE does not fit int32: wrap int64 colours to 32 bits)
+                rgb = ((((rgb.to(torch.int64) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)).contiguous()
+            if xyz.shape[0] != rgb.shape[0]:
+                raise ValueError("xyz and rgb lengths differ")
+            check(lib().vr_scene_edit(self.handle, c_void_p(xyz.data_ptr()), c_void_p(rgb.data_ptr()), rgb.shape[0], 1,
+                                      sp), "vr_scene_edit")
+            return
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint32).reshape(-1)
+        if xyz.shape[0] != rgb.shape[0]:
+            raise ValueError("xyz and rgb lengths differ")
+        check(lib().vr_scene_edit(self.handle, xyz.ctypes.data_as(c_void_p), rgb.ctypes.data_as(c_void_p),
+                                  rgb.shape[0], 0, sp), "vr_scene_edit")
+
+    def voxels(self, device: bool = False, stream=None):
+        """vr_scene_voxels: the scene's voxels, (xyz int32[n,3], rgb uint32[n]) as numpy arrays,
+        or (device=True) as torch tensors on the scene's device (rgb as int32 words).  Ordered
+        by region index, then by the store's key order."""
+        n = c_size_t()
+        check(lib().vr_scene_voxels(self.handle, None, None, 0, 0, None, ctypes.byref(n)), "vr_scene_voxels")
+        sp = _stream_ptr(stream)
+        if device:
+            dev = torch.device("cuda", self.info()["device"])
+            xyz = torch.empty((n.value, 3), dtype=torch.int32, device=dev)
+            rgb = torch.empty(n.value, dtype=torch.int32, device=dev)
+            if n.value:
+                check(lib().vr_scene_voxels(self.handle, c_void_p(xyz.data_ptr()), c_void_p(rgb.data_ptr()), n.value, 1,
+                                            sp, ctypes.byref(n)), "vr_scene_voxels")
+            return xyz, rgb
+        xyz = np.zeros((max(n.value, 1), 3), dtype=np.int32)
+        rgb = np.zeros(max(n.value, 1), dtype=np.uint32)
+        check(lib().vr_scene_voxels(self.handle, xyz.ctypes.data_as(c_void_p), rgb.ctypes.data_as(c_void_p), n.value, 0,
+                                    sp, ctypes.byref(n)), "vr_scene_voxels")
+        return xyz[: n.value].copy(), rgb[: n.value].copy()
 
     def close(self) -> None:
         if self._h:

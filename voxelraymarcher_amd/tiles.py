@@ -7,6 +7,10 @@ gather of the framebuffer to rank 0.  Two layouts (include/vr.h):
                rank (j + stride * b) % R (vr_render_tiles): every rank gets a share of every
                band, so a cluster of expensive rows (C5's crawl rows) is spread over all ranks
                while each 8x8 wave tile stays whole.
+
+Every rank holds its own scene, and edits (DeviceScene.edit) do not travel between ranks: a
+caller that edits applies the same batch on every rank.  The edit is deterministic, so the
+ranks' images (DeviceScene.digest) stay identical and the tiles of one frame still fit.
 """
 from __future__ import annotations
 
