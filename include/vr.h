@@ -175,6 +175,56 @@ int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n
 int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capacity,
                     int outputs_on_device, void* stream, size_t* n_out);
 
+/* vr_hit.status */
+#define VR_HIT_MISS    0u  /* the walk left the scene: the pixel is background */
+#define VR_HIT_VOXEL   1u  /* the walk read a stored voxel */
+#define VR_HIT_NEVER   2u  /* the reference's primary walk would never finish (the render writes 0) */
+#define VR_HIT_OUTSIDE 3u  /* px >= width or py >= height: no ray */
+
+/* The primary hit behind one pixel: what the rendered pixel was shaded from. */
+typedef struct {            /* 64 bytes, 16-byte aligned records */
+    uint32_t status;        /* VR_HIT_* ; every other field is 0 unless VOXEL */
+    uint32_t color;         /* the stored colour the walk read (0x00RRGGBB, unlit) */
+    int32_t  voxel[3];      /* world voxel coordinates: what vr_scene_edit / vr_scene_voxels use */
+    int32_t  normal[3];     /* the normal the lighting used: one component +-1, others 0 */
+    int32_t  region[3];     /* currentRegion at the hit */
+    float    point[3];      /* region-local hit location: applyLighting's point, the shadow ray's origin */
+    uint32_t reserved[2];   /* 0 */
+} vr_hit;
+
+/* Which voxel, face and hit point lie behind pixels of a frame: for each of n queries the hit
+ * that vr_render's pixel (px[i], py[i]) -- the word at py * width + px, y = 0 the top row --
+ * is shaded from, for the same scene, algorithm, camera, translation, scale and frame size.
+ * The ray and the primary walk are the render's, bit for bit (walks of any length run to
+ * their end; one the reference would never finish gives VR_HIT_NEVER).  No lighting is taken:
+ * only the primary walk runs, no shadow walk.
+ *
+ *   voxel   the stored voxel whose colour the walk read, in world voxel coordinates
+ *           (region * 64 + the matched key's local x, y, z): vr_scene_voxels contains
+ *           (voxel, color), and vr_scene_edit takes it as it is.
+ *   normal  the REFERENCE's normal, the one the lighting used (getNormalFromTValues,
+ *           Renderer.cuh:237-247, or the axis step's): not always the geometric face the ray
+ *           crossed.  voxel + normal is usually the empty neighbour to build on, but that
+ *           is not guaranteed.
+ *   point   region-local.  The scene-space position is region * 64 + point; the lighting's
+ *           world point is translation + region * 64 + point (unscaled, as the reference's).
+ *
+ * px, py: n uint32 each, on the scene's device when inputs_on_device != 0; hits: n records,
+ * on the device (16-byte aligned) when outputs_on_device != 0.  Host arrays are staged
+ * through device buffers the call allocates and frees; with everything on the device it
+ * allocates nothing.  The work runs on `stream` and the call returns when hits[0..n) are
+ * written, as vr_scene_voxels does.  n == 0 returns VR_OK and does nothing.
+ *
+ * A pick is not a render launch: it takes no slot of the per-device ring, learns and forgets
+ * no order, and renders before and after it behave as if it had not happened.
+ *
+ * VR_E_INVALID: s, cam or translation NULL; px, py or hits NULL with n > 0; width or height
+ * outside 1..65536; n >= 2^31; an unknown algorithm; a stream that is capturing a HIP graph. */
+int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam,
+            const float translation[3], uint32_t scale, uint32_t width, uint32_t height,
+            const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
+            vr_hit* hits, int outputs_on_device, void* stream);
+
 /* rayMarchSceneOriginal / rayMarchSceneJumpAxis (Renderer.cuh:1033-1063) as
  * launched by runRaymarchingKernel (Main.cu:105-163), for image rows
  * [row_begin, row_end) of a width x height frame.  out_dev: device buffer of

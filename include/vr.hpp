@@ -143,4 +143,19 @@ inline void runRaymarchingKernel(uint32_t width, uint32_t height, RayMarchAlgori
           "runRaymarchingKernel");
 }
 
+// vr_pick: the hit behind each pixel (px[i], py[i]) of the frame runRaymarchingKernel renders
+// for the same arguments -- the voxel (what vr_scene_edit takes), the reference's shading
+// normal and the hit point.  Host arrays in, host records out; returns when they are written.
+inline std::vector<vr_hit> pick(uint32_t width, uint32_t height, RayMarchAlgorithm algo, const Camera& camera,
+                                const VoxelSceneInfo& info, const DeviceScene& scene, const std::vector<uint32_t>& px,
+                                const std::vector<uint32_t>& py, void* stream = nullptr) {
+    if (px.size() != py.size()) throw Error(VR_E_INVALID, "pick: px and py lengths differ");
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<vr_hit> hits(px.size());
+    check(vr_pick(scene.get(), (vr_algo)algo, &camera.raw(), t, info.scale, width, height, px.data(), py.data(), px.size(),
+                  0, hits.data(), 0, stream),
+          "pick");
+    return hits;
+}
+
 }  // namespace vrx

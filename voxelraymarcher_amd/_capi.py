@@ -63,6 +63,15 @@ class VrRenderOpts(ctypes.Structure):
 
 VR_RENDER_OPTS_MIN_SIZE = 48
 
+VR_HIT_MISS, VR_HIT_VOXEL, VR_HIT_NEVER, VR_HIT_OUTSIDE = 0, 1, 2, 3
+
+
+class VrHit(ctypes.Structure):
+    """vr_hit: the primary hit behind one pixel (64 bytes)."""
+    _fields_ = [("status", c_uint32), ("color", c_uint32), ("voxel", c_int32 * 3), ("normal", c_int32 * 3),
+                ("region", c_int32 * 3), ("point", c_float * 3), ("reserved", c_uint32 * 2)]
+
+
 
 class VrError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str):
@@ -107,6 +116,8 @@ SIGNATURES = {
     "vr_render_opts_init": (c_int, [POINTER(VrRenderOpts)]),
     "vr_render_count": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float),
                                 c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "vr_pick": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(c_float), c_uint32, c_uint32, c_uint32, c_void_p,
+                        c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
     "vr_synth_generate": (c_int, [POINTER(VrSynthParams), POINTER(c_int32), POINTER(c_uint32), c_size_t,
                                   POINTER(c_size_t)]),
@@ -150,6 +161,7 @@ def f3(v) -> ctypes.Array:
 __all__ = ["lib", "check", "VrCamera", "VrLighting", "VrRenderOpts", "VR_RENDER_OPTS_MIN_SIZE", "VR_KERNEL_AUTO",
            "VR_KERNEL_TILE", "VR_KERNEL_TILE_REWALK", "VR_SCHEDULE_AUTO", "VR_SCHEDULE_GRID",
            "VR_SCHEDULE_HEAVIEST_FIRST", "VR_OCCUPANCY_AUTO", "VR_OCCUPANCY_LONE", "VR_OCCUPANCY_IN_FLIGHT",
-           "VrSceneInfo", "VrSynthParams", "VrError", "SIGNATURES",
+           "VrSceneInfo", "VrSynthParams", "VrHit", "VR_HIT_MISS",
+           "VR_HIT_VOXEL", "VR_HIT_NEVER", "VR_HIT_OUTSIDE", "VrError", "SIGNATURES",
            "VR_STORE_VCS", "VR_STORE_HASHTABLE", "VR_ALGO_LONGESTAXIS", "VR_ALGO_ORIGINAL", "f3", "LIB_PATH",
            "c_uint8"]

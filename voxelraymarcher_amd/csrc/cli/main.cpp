@@ -9,6 +9,9 @@
 //                   [--gpus N]   (the frame image-tiled over devices 0..N-1 of the node and
 //                                 gathered to device 0 over RCCL: multi_gpu.h; N = 1 takes the
 //                                 same RCCL path with one rank)
+//                   [--pick X,Y]...  (after the frame is rendered: one line per pick with the
+//                                 voxel, stored colour and shading normal behind pixel (X, Y),
+//                                 y = 0 the top row -- vr_pick; not with --gpus N > 1)
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -44,6 +47,24 @@ bool parse_vec3(const char* s, float out[3]) {
     return *s == 0;
 }
 
+// "X,Y" -> two unsigned 32-bit decimals; false on malformed input.
+bool parse_pixel(const char* s, uint32_t& x, uint32_t& y) {
+    uint32_t* out[2] = {&x, &y};
+    for (int i = 0; i < 2; ++i) {
+        if (*s < '0' || *s > '9') return false;
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(s, &end, 10);
+        if (v > 0xFFFFFFFFull) return false;
+        *out[i] = (uint32_t)v;
+        s = end;
+        if (i == 0) {
+            if (*s != ',') return false;
+            ++s;
+        }
+    }
+    return *s == 0;
+}
+
 bool is_integer(const char* s) {
     if (!s || !*s) return false;
     if (*s == '-' || *s == '+') ++s;
@@ -71,6 +92,7 @@ int main(int argc, char* argv[]) {
     int device = 0, repeat = 1, gpus = 0;
     bool multi = false;                      // --gpus given: the RCCL-tiled frame
     bool shadows = true, point_light = false, has_dir = false;
+    std::vector<uint32_t> pick_x, pick_y;    // --pick X,Y (repeatable)
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -94,10 +116,21 @@ int main(int argc, char* argv[]) {
         else if (a == "--point-light") { point_light = true; vec3("--point-light", next("--point-light"), light_pos); }
         else if (a == "--light-dir") { has_dir = true; vec3("--light-dir", next("--light-dir"), light_dir); }
         else if (a == "--light-color") vec3("--light-color", next("--light-color"), light_color);
+        else if (a == "--pick") {
+            const char* v = next("--pick");
+            uint32_t x = 0, y = 0;
+            if (!parse_pixel(v, x, y)) {
+                std::cerr << "--pick needs X,Y (pixel coordinates)" << std::endl;
+                std::exit(2);
+            }
+            pick_x.push_back(x);
+            pick_y.push_back(y);
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
-                         "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N]" << std::endl;
+                         "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
+                         "[--pick X,Y]..." << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -110,6 +143,10 @@ int main(int argc, char* argv[]) {
         }
         std::cout << "wrote " << vxb_path << std::endl;
         return 0;
+    }
+    if (!pick_x.empty() && multi && gpus > 1) {
+        std::cerr << "ERROR: --pick is a single-GPU query: not with --gpus " << gpus << std::endl;
+        return 2;
     }
     // argv[1] = scale (Main.cu:181-186); optional here (README.md:22-25 omits it).
     uint32_t scale = 1;
@@ -178,6 +215,21 @@ int main(int argc, char* argv[]) {
         lit.use_point_light = point_light;                       // Main.cu:37
         lit.use_shadows = shadows;                               // Main.cu:40
 
+        // --pick: the hit each picked pixel of the rendered frame was shaded from (vr_pick)
+        auto print_picks = [&]() {
+            if (pick_x.empty()) return;
+            const std::vector<vr_hit> hits = vrx::pick(width, height, algo, camera, sinfo, scene, pick_x, pick_y);
+            for (size_t i = 0; i < hits.size(); ++i) {
+                const vr_hit& h = hits[i];
+                if (h.status == VR_HIT_VOXEL)
+                    std::printf("pick %u %u voxel %d %d %d color 0x%06X normal %d %d %d\n", pick_x[i], pick_y[i], h.voxel[0],
+                                h.voxel[1], h.voxel[2], h.color, h.normal[0], h.normal[1], h.normal[2]);
+                else
+                    std::printf("pick %u %u %s\n", pick_x[i], pick_y[i],
+                                h.status == VR_HIT_MISS ? "miss" : (h.status == VR_HIT_NEVER ? "never" : "outside"));
+            }
+            std::fflush(stdout);
+        };
         if (multi) {
             // The frame image-tiled over devices 0..gpus-1, RCCL-gathered to device 0 (multi_gpu.h)
             vrx::MultiGpuFrame mg;
@@ -201,6 +253,7 @@ int main(int argc, char* argv[]) {
             for (size_t i = 0; i < best.rank_render_ms.size(); ++i)
                 std::cout << "  rank " << i << " render " << (long long)(best.rank_render_ms[i] * 1000.0f)
                           << " microseconds" << std::endl;
+            print_picks();                   // (--gpus 1: the scene of this process's device)
             std::vector<uint8_t> host;
             if (!mg.download(host)) {
                 std::cerr << "ERROR: " << mg.error() << std::endl;
@@ -233,6 +286,7 @@ int main(int argc, char* argv[]) {
         std::cout << hipGetErrorString(hipGetLastError()) << std::endl;
         std::cout << "Execution Time for Ray Marching Algorithm is: " << (long long)(best_ms * 1000.0f)
                   << " microseconds (" << (double)width * height / (best_ms * 1e3) << " Mrays/s)" << std::endl;
+        print_picks();
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,
         // async copy into pinned memory, parallel PNG encode (vr_png_write).
         const size_t nbytes = (size_t)width * height * 3;

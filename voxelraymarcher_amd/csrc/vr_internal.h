@@ -185,6 +185,12 @@ hipError_t launch_march(int store, int algo, bool count, const KScene& s, const 
                         hipStream_t stream, uint32_t crawl_wgs, bool in_flight, bool crawl = true);
 // Crawl-pass grid for a launch that expects about `records` deferred pixels.
 uint32_t crawl_grid(uint32_t records, uint32_t rpw);
+// vr_pick's kernel: the primary hit behind each of n pixels (px[i], py[i]) of the view's frame
+// as 64-byte vr_hit records (hits: 16-byte aligned device memory), one lane per query with the
+// exact walker.  The view is make_view's with one band over the frame; nothing below `out` is read.
+constexpr uint32_t kPickMiss = 0, kPickVoxel = 1, kPickNever = 2, kPickOutside = 3;   // = VR_HIT_*
+hipError_t launch_pick(int store, int algo, const KScene& s, const KView& v, const uint32_t* px, const uint32_t* py,
+                       uint32_t n, void* hits, hipStream_t stream);
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);
 // ht_filter of a cuckoo scene from its tables (one workgroup per region).

@@ -1,6 +1,6 @@
 // vr_launch.cpp -- the render launch: the per-device slot ring, the learned orders and the
 // crawl-pass skip kept per slot (their decisions: vr_launch_plan.h), and the render entry
-// points of include/vr.h.
+// points of include/vr.h; vr_pick, which shares the view but none of the launch state.
 //
 // Replaces runRaymarchingKernel (main/Main.cu:105-163).
 #include <algorithm>
@@ -562,6 +562,75 @@ int vr_render_ex(const vr_scene* s, vr_algo algo, const vr_camera* cam, const vr
     v.defer_cap = o.defer_cap;
     if (o.schedule > VR_SCHEDULE_HEAVIEST_FIRST) return fail(VR_E_INVALID, "unknown schedule");
     return launch(s, algo, o.kernel, o.schedule, o.occupancy, v, stream);
+}
+
+// The hit behind each pixel (vr.h).  Not a render launch: no slot lease, no view key, no
+// D.follow / D.alone bookkeeping -- nothing the render path keeps per device is touched.
+int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam, const float translation[3], uint32_t scale,
+            uint32_t width, uint32_t height, const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
+            vr_hit* hits, int outputs_on_device, void* stream) {
+    static_assert(sizeof(vr_hit) == 64 && offsetof(vr_hit, voxel) == 8 && offsetof(vr_hit, normal) == 20 &&
+                      offsetof(vr_hit, region) == 32 && offsetof(vr_hit, point) == 44 && offsetof(vr_hit, reserved) == 56,
+                  "vr_hit: the record pick_kernel writes");
+    static_assert(vr::kPickMiss == VR_HIT_MISS && vr::kPickVoxel == VR_HIT_VOXEL && vr::kPickNever == VR_HIT_NEVER &&
+                      vr::kPickOutside == VR_HIT_OUTSIDE, "VR_HIT_*");
+    if (!s) return fail(VR_E_INVALID, "vr_pick: scene is NULL");
+    if (!cam || !translation) return fail(VR_E_INVALID, "vr_pick: camera/translation NULL");
+    if (n && (!px || !py || !hits)) return fail(VR_E_INVALID, "vr_pick: px/py/hits NULL");
+    if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "vr_pick: bad image size");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_pick: too many queries");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_pick: unknown algorithm");
+    if (n == 0) return VR_OK;
+    // the view of a whole-frame render: one band, rank 0 of 1 (the lights are never read)
+    vr_lighting lit;
+    vr_lighting_default(&lit);
+    vr::KView v;
+    int rc = make_view(s, cam, &lit, translation, scale, width, height, v);
+    if (rc) return rc;
+    v.row_limit = height;
+    v.band_rows = height;
+    v.band_minv = height == 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / height);
+    v.nranks = 1;
+    v.local_rows = height;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(VR_E_INVALID, "vr_pick cannot be captured into a HIP graph (stream is capturing)");
+    const uint32_t *dpx = px, *dpy = py;
+    void *tq = nullptr, *th = nullptr;      // staging owned by this call: {px, py}, hits
+    auto release = [&]() {
+        if (tq) (void)hipFree(tq);
+        if (th) (void)hipFree(th);
+    };
+    if (!inputs_on_device) {
+        e = hipMalloc(&tq, 2 * n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(tq, px, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((uint32_t*)tq + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { release(); return hip_fail(e, "vr_pick: query upload"); }
+        dpx = (const uint32_t*)tq;
+        dpy = dpx + n;
+    }
+    void* dh = hits;
+    if (!outputs_on_device) {
+        e = hipMalloc(&th, n * sizeof(vr_hit));
+        if (e != hipSuccess) { release(); return hip_fail(e, "vr_pick: hit buffer"); }
+        dh = th;
+    } else if (((uintptr_t)hits & 15u) != 0u) {
+        release();
+        return fail(VR_E_INVALID, "vr_pick: device hits must be 16-byte aligned");
+    }
+    e = vr::launch_pick((int)s->store, (int)algo, vr::kscene(s), v, dpx, dpy, (uint32_t)n, dh, st);
+    if (e == hipSuccess && !outputs_on_device)
+        e = hipMemcpyAsync(hits, th, n * sizeof(vr_hit), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    release();
+    if (e != hipSuccess) return hip_fail(e, "vr_pick");
+    return VR_OK;
 }
 
 int vr_render_opts_init(vr_render_opts* opts) {

@@ -217,8 +217,14 @@ __device__ __forceinline__ uint32_t* tile_prim() {
 // through its walk loop: C4 0.085 -> 0.109 ms per frame, profiles/r03/ab_exact_cuckoo.txt.)
 template <int STORE, bool CRAWL>
 struct ExactWalk { static constexpr bool value = CRAWL; };
-template <int STORE, bool COUNT, bool CRAWL>
-struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget : kTileBudget> {
+// PICK (pick_kernel only): the walk also brings out the grid cell of the probe that read the
+// primary hit's colour (PickCell::pv, region-local, as probed).  Every write to it sits under
+// `if constexpr (PICK)` and the render and crawl kernels' walkers have no such member, so
+// those kernels carry no extra value (their resource usage is unchanged: profiles/pick/).
+template <bool PICK> struct PickCell {};
+template <> struct PickCell<true> { i3 pv{0, 0, 0}; };
+template <int STORE, bool COUNT, bool CRAWL, bool PICK = false>
+struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget : kTileBudget>, PickCell<PICK> {
     using C = Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget : kTileBudget>;
     static constexpr bool kExact = ExactWalk<STORE, CRAWL>::value;
     static constexpr uint32_t kBudget = C::kBudget;
@@ -736,6 +742,8 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
             h.so = o;
             h.region = cr;
             h.longest = false;
+            // (a hit keeps o unstepped: the probed voxel)
+            if constexpr (PICK) this->pv = i3{f2i(o.x), f2i(o.y), f2i(o.z)};
         }
         return true;
     }
@@ -824,6 +832,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                     h.col = col;
                     h.region = cr;
                     h.longest = true;
+                    if constexpr (PICK) this->pv = pg;
                     if (jumping) {                   // performVoxelSpaceJump's hit
                         h.nc = normal_from_t(tX, tY, tZ, tMin, ds);
                         h.so = old_o;
@@ -1125,6 +1134,10 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
             }
             if (ex != kGo || hit) {
                 why = ex != kGo ? ex : kHit;
+                if constexpr (PICK && !SHADOW) {     // the stopping slot's cell (A, B or C)
+                    if (why == kHit)
+                        this->pv = stop == 0u ? to_i3(gL, AM, AS) : (stop == 1u ? to_i3(gL, CM, CS) : to_i3(CL, CM, CS));
+                }
                 break;
             }
             if (jumping && stop == 3u) {
@@ -1913,6 +1926,50 @@ __global__ __launch_bounds__(64 * kCrawlWaves) void crawl_kernel(KScene s, KView
     }
 }
 
+// Pick (vr_pick): the primary hit of pixel (px[i], py[i]) as a 64-byte record, one lane per
+// query, with the exact walker (the crawl pass's: every walk runs to its end, crawls are
+// fast-forwarded, a walk that never finishes is detected) and nothing else -- no lighting,
+// no shadow walk, no deferral, no byte count.  The view is one band over the whole frame
+// (rank 0 of 1), so pixel_ray maps (x, l) to frame pixel (x, y) as a full-frame render does.
+// The hit voxel is the cell of the probe that read the colour (PickCell), through the
+// store's key x << 20 | y << 10 | z and back: for a cell inside the region that is the
+// cell itself; a probe outside it can only match the stored voxel its wrapped key names.
+constexpr uint32_t kPickThreads = 256;
+template <int STORE, int ALGO>
+__global__ __launch_bounds__(kPickThreads) void pick_kernel(KScene s, KView v, const uint32_t* __restrict__ px,
+                                                           const uint32_t* __restrict__ py, uint32_t n,
+                                                           uint4* __restrict__ hits) {
+    const uint32_t i = blockIdx.x * kPickThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = px[i], y = py[i];
+    uint4 r0{kPickOutside, 0u, 0u, 0u}, r1{0u, 0u, 0u, 0u}, r2{0u, 0u, 0u, 0u}, r3{0u, 0u, 0u, 0u};
+    f3 ro, rd;
+    if (x < v.W && y < v.H && pixel_ray<true>(v, x, y, ro, rd)) {
+        Walker<STORE, false, true, true> w(s, v);
+        Hit h;
+        const bool hit = w.template primary<ALGO>(ro, rd, h);
+        r0.x = w.aborted ? kPickNever : (hit ? kPickVoxel : kPickMiss);
+        if (hit && !w.aborted) {
+            const uint32_t key = ((uint32_t)w.pv.x << 20) | ((uint32_t)w.pv.y << 10) | (uint32_t)w.pv.z;
+            const f3 nrm = w.normal_of(h.nc);
+            r0.y = h.col;
+            r0.z = (uint32_t)(h.region.x * kBlock) + (key >> 20);
+            r0.w = (uint32_t)(h.region.y * kBlock) + ((key >> 10) & 1023u);
+            r1.x = (uint32_t)(h.region.z * kBlock) + (key & 1023u);
+            r1.y = (uint32_t)(int32_t)nrm.x;
+            r1.z = (uint32_t)(int32_t)nrm.y;
+            r1.w = (uint32_t)(int32_t)nrm.z;
+            r2 = uint4{(uint32_t)h.region.x, (uint32_t)h.region.y, (uint32_t)h.region.z, __float_as_uint(h.so.x)};
+            r3 = uint4{__float_as_uint(h.so.y), __float_as_uint(h.so.z), 0u, 0u};
+        }
+    }
+    uint4* rec = hits + (size_t)i * 4u;        // four 16-byte stores
+    rec[0] = r0;
+    rec[1] = r1;
+    rec[2] = r2;
+    rec[3] = r3;
+}
+
 // KScene::vcs_cbits: thread (r, w) ORs the existence of cluster slots 32w..32w+31 of
 // region r (a present cluster's record has an index in every word, vr_internal.h)
 __global__ void cluster_bits_kernel(const uint2* __restrict__ mask, uint32_t n_regions, uint32_t* __restrict__ cbits) {
@@ -2064,6 +2121,21 @@ hipError_t launch_march(int store, int algo, bool count, const KScene& s, const 
 #endif
 #undef VR_LAUNCH
 #undef VR_LAUNCH_HI
+    return hipGetLastError();
+}
+
+hipError_t launch_pick(int store, int algo, const KScene& s, const KView& v, const uint32_t* px, const uint32_t* py,
+                       uint32_t n, void* hits, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + kPickThreads - 1u) / kPickThreads), block(kPickThreads);
+    uint4* out = static_cast<uint4*>(hits);
+#define VR_PICK(ST, AL) hipLaunchKernelGGL((pick_kernel<ST, AL>), grid, block, 0, stream, s, v, px, py, n, out)
+    if (store == STORE_VCS) {
+        if (algo == ALGO_ORIGINAL) VR_PICK(STORE_VCS, ALGO_ORIGINAL); else VR_PICK(STORE_VCS, ALGO_LONGEST);
+    } else {
+        if (algo == ALGO_ORIGINAL) VR_PICK(STORE_HASH, ALGO_ORIGINAL); else VR_PICK(STORE_HASH, ALGO_LONGEST);
+    }
+#undef VR_PICK
     return hipGetLastError();
 }
 

@@ -166,6 +166,10 @@ class DeviceScene:
                                     sp, ctypes.byref(n)), "vr_scene_voxels")
         return xyz[: n.value].copy(), rgb[: n.value].copy()
 
+    def pick(self, algorithm, camera, info, width: int, height: int, px, py, stream=None):
+        """vr_pick with this scene: see pick()."""
+        return pick(self, algorithm, camera, info, width, height, px, py, stream=stream)
+
     def close(self) -> None:
         if self._h:
             lib().vr_scene_destroy(self._h)
@@ -446,6 +450,59 @@ def render_count(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camer
     """Instrumented render: adds the SURVEY 8(d) algorithmic bytes into counter (int64 cuda scalar)."""
     render_ex(scene, algorithm, camera, lighting, info, width, height, out, row_begin, row_end,
               counter=counter, kernel=kernel, stream=stream)
+
+
+class HitStatus(enum.IntEnum):
+    """vr_hit.status (VR_HIT_*)."""
+    MISS = _capi.VR_HIT_MISS          # the walk left the scene: background
+    VOXEL = _capi.VR_HIT_VOXEL        # the walk read a stored voxel
+    NEVER = _capi.VR_HIT_NEVER        # the reference's walk would never finish (the render writes 0)
+    OUTSIDE = _capi.VR_HIT_OUTSIDE    # the pixel is outside the frame: no ray
+
+
+# vr_hit, field for field (64 bytes)
+HIT_DTYPE = np.dtype([("status", "<u4"), ("color", "<u4"), ("voxel", "<i4", (3,)), ("normal", "<i4", (3,)),
+                      ("region", "<i4", (3,)), ("point", "<f4", (3,)), ("reserved", "<u4", (2,))])
+assert HIT_DTYPE.itemsize == ctypes.sizeof(_capi.VrHit) == 64
+
+
+def pick(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, width: int,
+         height: int, px, py, stream=None):
+    """vr_pick: the voxel, face and hit point behind pixels (px[i], py[i]) of the width x height
+    frame that run_raymarching_kernel renders for the same scene, algorithm, camera and info --
+    exactly the hit each pixel is shaded from (y = 0 is the top row).  numpy (or list) px/py
+    give a numpy structured array of HIT_DTYPE; CUDA int32/uint32 tensors on the scene's
+    device give an (n, 16) int32 CUDA tensor of the same bytes.  `voxel` is what
+    DeviceScene.edit takes; `normal` is the reference's shading normal.  Runs on `stream`
+    (default: the current stream) and returns when the records are written."""
+    sp = _stream_ptr(stream)
+    args = (scene.handle, int(algorithm), ctypes.byref(camera.raw), f3(info.translation), int(info.scale), int(width),
+            int(height))
+    if hasattr(px, "is_cuda") and px.is_cuda:
+        if not (hasattr(py, "is_cuda") and py.is_cuda) or px.device != py.device:
+            raise TypeError("px and py must both be CUDA tensors on one device")
+        for t in (px, py):
+            if t.dtype not in (torch.int32, torch.uint32):
+                raise TypeError("px/py must be int32 or uint32 tensors")
+        px, py = px.contiguous().reshape(-1), py.contiguous().reshape(-1)
+        if px.shape[0] != py.shape[0]:
+            raise ValueError("px and py lengths differ")
+        n = px.shape[0]
+        hits = torch.empty((n, 16), dtype=torch.int32, device=px.device)
+        if n:
+            check(lib().vr_pick(*args, c_void_p(px.data_ptr()), c_void_p(py.data_ptr()), n, 1,
+                                c_void_p(hits.data_ptr()), 1, sp), "vr_pick")
+        return hits
+    px = np.ascontiguousarray(px, dtype=np.uint32).reshape(-1)
+    py = np.ascontiguousarray(py, dtype=np.uint32).reshape(-1)
+    if px.shape[0] != py.shape[0]:
+        raise ValueError("px and py lengths differ")
+    n = px.shape[0]
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    if n:
+        check(lib().vr_pick(*args, px.ctypes.data_as(c_void_p), py.ctypes.data_as(c_void_p), n, 0,
+                            hits.ctypes.data_as(c_void_p), 0, sp), "vr_pick")
+    return hits
 
 
 def band_buffer_words(width: int, height: int, band_rows: int, nranks: int) -> int:
