@@ -388,6 +388,17 @@ int vr_debug_skip_next_crawl(int device);
 int vr_debug_capture_lane_order(int device);
 int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t pcost_words, uint8_t* perm,
                         uint64_t perm_bytes);
+/* Test hook: whether the device's launches rendered under learned orders.  Host counters kept
+ * by the render launch, monotonic for the life of the process (vr_forget_orders does not reset
+ * them); vr_pick moves none.  out[0] render launches that reached the tile pass, [1] lane
+ * orders made, [2] launches whose tile pass had a lane order bound, [3] work orders made,
+ * [4] launches whose tile pass had a work order bound, [5] launches whose crawl pass was
+ * skipped, [6] the slots of the device's ring (a slot uses an order only when it comes round
+ * again, so a view is under its orders from launch slots + 1 on), [7] lane block width << 16 |
+ * height, in pixels.  Reads host state only and never initialises the device: for a device
+ * that has not rendered, [0..5] are 0.  VR_E_INVALID for a NULL out or a device outside 0..63.
+ * Never needed by a renderer. */
+int vr_debug_order_uses(int device, uint64_t out[8]);
 /* Every vr_render* call returns VR_E_INVALID on a stream that is capturing a HIP graph
  * (its per-device slot ring and work-order bookkeeping are host state that a graph replay
  * would not repeat). */

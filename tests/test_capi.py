@@ -256,3 +256,26 @@ def test_parallel_csv_parse_matches_python(tmp_path):
     with pytest.raises(vr.VrError) as e:
         vr.read_voxel_file(p)
     assert e.value.code == -6 and f":{bad_at + 1}:" in str(e.value)
+
+
+def test_order_uses_hook_on_a_device_that_never_rendered():
+    """vr_debug_order_uses (include/vr.h): host bookkeeping only, no HIP call.  A device that
+    has not rendered reports zero launches, orders, uses and skips, and the two constants the
+    learned-order tests size themselves by: the ring's 16 slots and the 16x32 lane block.  This
+    is the one place that pins the two constants as literals (every other test reads them from
+    the hook), so a deliberate change of the ring or of the block shape is made here as well."""
+    d = vr.debug_order_uses(61)
+    assert list(d) == ["launches", "lane_orders_made", "lane_order_uses", "work_orders_made", "work_order_uses",
+                       "crawl_skips", "slots", "lane_block"]
+    assert [d[k] for k in list(d)[:6]] == [0] * 6
+    assert d["slots"] == 16 and d["lane_block"] == (16, 32)
+    raw = (ctypes.c_uint64 * 8)(*[7] * 8)
+    assert vr.lib().vr_debug_order_uses(0, raw) == 0
+    assert raw[6] == 16 and raw[7] == (16 << 16 | 32)
+    assert vr.debug_order_uses(61) == d                      # reading moves nothing
+    for bad in (-1, 64):
+        with pytest.raises(vr.VrError) as e:
+            vr.debug_order_uses(bad)
+        assert e.value.code == -1
+    assert vr.lib().vr_debug_order_uses(61, None) == -1      # VR_E_INVALID: out is NULL
+    assert b"NULL" in vr.lib().vr_last_error()

@@ -20,6 +20,7 @@ from tests.crawl_views import points_scene
 from tests.edit_cases import VOXEL_REMOVE, apply_edits, sort_voxels, split_case
 from tests.fuzz_cases import make_case, make_wide_case
 from tests.helpers import diff_report, gpu_render, oracle_camera_from, oracle_lighting_from
+from tests.test_gpu_parity import check_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +112,9 @@ def test_frames_of_the_edited_scene(kind, seed, store):
         got, gbytes = gpu_render(gpu, algo, cam, lit, info, W, H, count=True)
         assert np.array_equal(got, want), f"{algo.name}: " + diff_report(got, want, W)
         assert gbytes == wbytes, f"{algo.name}: algorithmic bytes: gpu {gbytes} != oracle {wbytes}"
+        # and under the learned lane and work orders of the edited scene's view (check_frame)
+        check_frame(nxyz, nrgb, store, algo, W, H, c.scale, cam=cam, lit=lit, translation=c.translation,
+                    gpu_scene=gpu, want=(want, wbytes))
     gpu.close()
     ref.close()
 

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import oracle
-from tests.helpers import GOLDEN, diff_report, gpu_render, oracle_camera_from, oracle_lighting_from
+from tests.helpers import (GOLDEN, diff_report, gpu_render, oracle_camera_from, oracle_lighting_from,
+                           render_learned)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,18 @@ FRAMES = {f["name"]: f for f in json.load(open(os.path.join(GOLDEN, "frames.json
 
 def check_frame(xyz, rgb, store, algo, W, H, scale, cam=None, lit=None, translation=(0.0, 0.0, 0.0),
                 row_begin=0, row_end=None, count=True, oracle_scene=None, gpu_scene=None, kernels=KERNELS,
-                want=None, defer_caps=(0,)):
+                want=None, defer_caps=(0,), learned=True):
     """The GPU frame (every kernel; counted and uncounted; every deferral-list capacity)
     equals the oracle's pixels and algorithmic bytes.  want = (pixels, bytes) already
-    rendered by the oracle, else rendered here."""
+    rendered by the oracle, else rendered here.
+
+    learned: then the same view 2 * slots + 2 more times (tests/helpers.py render_learned),
+    so that its tile pass runs under the learned lane order and work order -- other pixels
+    per wave, another order of the tile groups, the crawl pass skipped where nothing
+    defers -- and every one of those launches equals the oracle's pixels too; then once
+    more through the instrumented kernel with the lane order bound, pixels and bytes.
+    vr_debug_order_uses tells that the orders really were bound.  (False only where the
+    stage pushes a test past a time bound the test itself asserts.)"""
     row_end = H if row_end is None else row_end
     cam = cam or vr.Camera.reference(W, H)
     lit = lit or vr.setup_constant_values()
@@ -50,6 +59,23 @@ def check_frame(xyz, rgb, store, algo, W, H, scale, cam=None, lit=None, translat
             got2, _ = gpu_render(scene, algo, cam, lit, info, W, H, row_begin, row_end, count=False, kernel=kernel,
                                  defer_cap=cap)
             assert np.array_equal(got2, want), f"{tag} (uncounted): " + diff_report(got2, want, W, row_begin)
+            if not learned:
+                continue
+            bad, first, d = render_learned(scene, algo, cam, lit, info, W, H, row_begin, row_end, want, kernel, cap)
+            assert not bad, f"{tag}: launches {bad} of {d['launches']} under learned orders differ: " + \
+                diff_report(first, want, W, row_begin)
+            assert d["lane_order_uses"] >= d["slots"] + 1, f"{tag}: the lane order was not bound: {d}"
+            # (AUTO on one waited-for stream: every launch is alone, so heaviest first)
+            assert d["work_order_uses"] >= d["slots"] + 1, f"{tag}: the work order was not bound: {d}"
+            device = scene.info()["device"]
+            bound = vr.debug_order_uses(device)["lane_order_uses"]
+            got3, gbytes3 = gpu_render(scene, algo, cam, lit, info, W, H, row_begin, row_end, count=True,
+                                       kernel=kernel, defer_cap=cap)
+            assert vr.debug_order_uses(device)["lane_order_uses"] == bound + 1, f"{tag}: counted launch, no lane order"
+            assert np.array_equal(got3, want), f"{tag} (counted, learned orders): " + \
+                diff_report(got3, want, W, row_begin)
+            if obytes is not None:
+                assert gbytes3 == obytes, f"{tag} (learned orders): algorithmic bytes: gpu {gbytes3} != oracle {obytes}"
     return want
 
 

@@ -351,7 +351,9 @@ def test_pick_leaves_renders_alone():
     allx, ally = frame_pixels(CW, CH)
     with vr.create_scene(xyz, rgb, VCS) as scene:
         frames = [gpu_render(scene, ORIGINAL, cam, lit, info, CW, CH)[0] for _ in range(3)]
+        uses = vr.debug_order_uses(0)
         recs = vr.pick(scene, ORIGINAL, cam, info, CW, CH, px, py)
+        assert vr.debug_order_uses(0) == uses      # (not a render launch: none of the eight values moves)
         frames.append(gpu_render(scene, ORIGINAL, cam, lit, info, CW, CH)[0])
         prep = vr.PreparedRender(scene, ORIGINAL, cam, lit, info, CW, CH)
         out = torch.full((CW * CH,), -1, dtype=torch.int32, device="cuda")
@@ -360,7 +362,9 @@ def test_pick_leaves_renders_alone():
         prep(out)
         torch.cuda.synchronize()
         frames.append(out.cpu().numpy().view(np.uint32))
+        uses = vr.debug_order_uses(0)
         every = vr.pick(scene, ORIGINAL, cam, info, CW, CH, allx, ally)
+        assert vr.debug_order_uses(0) == uses and uses["launches"] >= 6
     for f in frames[1:]:
         assert np.array_equal(f, frames[0])
     assert np.count_nonzero(frames[0]) >= 10

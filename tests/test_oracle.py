@@ -422,6 +422,70 @@ def test_fuzz_cases_python_restatement(seed):
                         where=(seed, store))
 
 
+def test_fuzz_cases_hold_a_whole_lane_block():
+    """The GPU fuzz (tests/test_gpu_fuzz.py) holds every case to the oracle under learned
+    orders too, but only a frame with a whole lane block deals pixels by the lane order
+    (blocks cut by the grid's edge keep the 8x8 tiles).  With the library's block shape
+    (vr_debug_order_uses), at least 85 % of the 300 cases hold one at their own W x H: today
+    264 do, those with H >= 25.  A change to fuzz_cases.py or to the block shape that moves
+    the fuzz off the learned path fails here."""
+    import voxelraymarcher_amd as vr
+    from tests.fuzz_cases import make_case, make_wide_case
+    from tests.helpers import full_lane_blocks
+    from tests.test_gpu_fuzz import SEEDS, WIDE_SEEDS
+    block = vr.debug_order_uses(0)["lane_block"]
+    cases = [make_case(s) for s in SEEDS] + [make_wide_case(s) for s in WIDE_SEEDS]
+    assert len(cases) == 300
+    n = sum(full_lane_blocks(c.W, c.H, block) >= 1 for c in cases)
+    print(f"{n} of {len(cases)} fuzz cases hold a whole {block[0]}x{block[1]} lane block")
+    assert n >= 0.85 * len(cases)
+
+
+def test_learned_order_seeds_are_what_the_cases_say():
+    """The fuzz seeds of tests/test_gpu_learned.py: every frame is at least 48 rows high (so
+    its odd row range keeps a whole row of lane blocks), and between them the cases hold point
+    lights, shadows off, scales 2, 3, 4 and 7, axis views, and zero-component and
+    equal-component lights.  A change to fuzz_cases.py that moves them elsewhere fails here."""
+    from tests.fuzz_cases import make_case, make_wide_case
+    from tests.test_gpu_learned import DEAL_SEEDS, SEEDS
+    cases = [make_wide_case(s) if s >= 5000 else make_case(s) for s in SEEDS]
+    assert len(cases) == 24 and set(DEAL_SEEDS) <= set(SEEDS)
+    assert all(c.H >= 48 for c in cases)
+    assert any(c.point for c in cases) and any(not c.shadows for c in cases)
+    assert {2, 3, 4, 7} <= {c.scale for c in cases}
+    assert any("axis view" in c.notes for c in cases)
+    dirs = [c.light_dir for c in cases if c.light_dir is not None]
+    assert any(0.0 in d for d in dirs) and any(abs(d[0]) == abs(d[1]) == abs(d[2]) for d in dirs)
+
+
+def test_learned_comparison_names_the_launch_and_the_pixel():
+    """The comparison behind render_learned (tests/helpers.py differing_launches), fed plain
+    CPU tensors: 34 frames of which launch 20 has one flipped word."""
+    torch = pytest.importorskip("torch")
+    from tests.helpers import diff_report, differing_launches
+    W, H, row_begin = 37, 23, 3
+    want = torch.arange(W * H, dtype=torch.int32)
+    frames = [want.clone() for _ in range(34)]
+    frames[20][11 * W + 5] ^= 1
+    bad, first = differing_launches(iter(frames), want)
+    assert bad == [20]
+    report = diff_report(first, want.numpy().view(np.uint32), W, row_begin)
+    assert "1 of 851 pixels differ" in report and "(x=5, y=14)" in report
+    assert differing_launches(iter(frames[:20]), want) == ([], None)
+    # the same buffer refilled for every launch, as render_learned does: each launch is compared
+    # before the next one overwrites it
+    buf = torch.empty_like(want)
+
+    def refilled():
+        for k in range(34):
+            buf.copy_(want)
+            if k in (7, 33):
+                buf[k] = -1
+            yield buf
+    bad, first = differing_launches(refilled(), want)
+    assert bad == [7, 33] and int(first[7]) == 0xFFFFFFFF and int(first[33]) == 33
+
+
 def test_cycle_detection_finds_every_period():
     """The region-level loops' never-finishes test (Brent's cycle detection, oracle
     cycle_step = the kernels' Ctx::cycle_step, DESIGN.md 2): a state sequence that

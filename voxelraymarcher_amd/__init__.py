@@ -12,7 +12,7 @@ from .output import FrameWriter, ImageWriter, encode_png, write_png
 from .renderer import (CONFIGS, HIT_DTYPE, VOXEL_REMOVE, Build, HitStatus, Camera, DeviceScene, Kernel, Occupancy, PreparedRender, RayMarchAlgorithm,
                        RenderConfig,
                        Schedule, StorageType, VoxelSceneCPU, VoxelSceneInfo, assemble_tiles_device, band_buffer_words,
-                       create_scene, deal_stride_default, debug_capture_lane_order, debug_lane_order, debug_skip_next_crawl,
+                       create_scene, deal_stride_default, debug_capture_lane_order, debug_lane_order, debug_order_uses, debug_skip_next_crawl,
                        forget_orders, pack_rgb8, pick, parse_algorithm, parse_storage,
                        read_voxel_file, render_bands, render_count, render_ex, render_tiles, run_raymarching_kernel,
                        setup_constant_values, synth_scene, tile_buffer_words, write_binary_scene, write_voxel_file)
@@ -21,7 +21,7 @@ __all__ = ["LIB_PATH", "VrError", "lib", "FrameWriter", "ImageWriter", "encode_p
            "VOXEL_REMOVE", "Build", "pick",
            "Camera", "DeviceScene", "Kernel", "Occupancy", "PreparedRender", "RayMarchAlgorithm", "RenderConfig", "Schedule",
            "StorageType", "VoxelSceneCPU", "VoxelSceneInfo", "assemble_tiles_device", "band_buffer_words",
-           "create_scene", "deal_stride_default", "debug_capture_lane_order", "debug_lane_order",
+           "create_scene", "deal_stride_default", "debug_capture_lane_order", "debug_lane_order", "debug_order_uses",
            "debug_skip_next_crawl", "forget_orders", "pack_rgb8", "parse_algorithm", "parse_storage",
            "read_voxel_file", "render_bands", "render_count", "render_ex", "render_tiles", "run_raymarching_kernel",
            "setup_constant_values", "synth_scene", "tile_buffer_words", "write_binary_scene", "write_voxel_file"]

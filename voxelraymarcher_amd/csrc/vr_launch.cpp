@@ -139,6 +139,9 @@ struct SlotRing {
         uint32_t last_idx = 0;
         uint64_t last_key = 0;             // the view of the device's previous launch
         bool force_skip = false;           // vr_debug_skip_next_crawl (tests)
+        // vr_debug_order_uses (tests): render launches, lane orders made, launches with a lane
+        // order bound, work orders made, launches with a work order bound, crawl passes skipped
+        uint64_t uses[6] = {0, 0, 0, 0, 0, 0};
         // vr_debug_capture_lane_order (tests): the next lane order made on the device is kept
         // here with the walk lengths it was made from, for vr_debug_lane_order
         bool capture_lane = false;
@@ -462,6 +465,10 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
     // the same pixels)
     const vr::KScene ks = vr::kscene(s);
     const uint32_t cwgs = vr::crawl_grid(expect, v.crawl_rpw);
+    D.uses[0] += 1u;
+    D.uses[2] += v.perm != nullptr;
+    D.uses[4] += v.order != nullptr;
+    D.uses[5] += !crawl;
     VR_HP(6);
     e = vr::launch_march((int)s->store, (int)algo, v.bytes != nullptr, ks, v, st, cwgs, pol.hi, crawl);
     VR_HP(7);
@@ -475,6 +482,7 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
         with_costs = order_enabled() && S.work.cost && S.work.cap >= n;
         e = vr::launch_perm(v.pcost, v.LW, v.local_rows, gx, gy, S.lane.perm, with_costs ? S.work.cost : nullptr, st);
         S.lane.learned(gx, gy, key, e == hipSuccess);
+        D.uses[1] += e == hipSuccess;
         S.work.relaned = !with_costs;
         if (e == hipSuccess && D.capture_lane) {     // (tests only: waits for the stream)
             D.capture_lane = false;
@@ -494,6 +502,7 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
         e = vr::launch_order(S.work.cost, n, gx, S.work.order, st);
         order_check(S.work, lease.idx, gx, gy);
         S.work.learned(gx, gy, key, e == hipSuccess);
+        D.uses[3] += e == hipSuccess;
     }
     if (v.pcost) {      // (a relaning launch's per-pixel walk lengths: transient)
         const hipError_t ef = hipFreeAsync(v.pcost, st);
@@ -693,6 +702,18 @@ int vr_debug_skip_next_crawl(int device) {
     SlotRing::Dev& D = g_defer_ring.dev[device];
     std::lock_guard<std::mutex> lk(D.mu);
     D.force_skip = true;
+    return VR_OK;
+}
+
+int vr_debug_order_uses(int device, uint64_t out[8]) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    if (!out) return fail(VR_E_INVALID, "out is NULL");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    const vr::LaneShape sh = vr::lane_shape();
+    std::lock_guard<std::mutex> lk(D.mu);
+    for (int i = 0; i < 6; ++i) out[i] = D.uses[i];
+    out[6] = g_defer_ring.nslots;
+    out[7] = (uint64_t)sh.block_x << 16 | sh.block_y;
     return VR_OK;
 }
 

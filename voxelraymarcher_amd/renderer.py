@@ -565,6 +565,22 @@ def debug_lane_order(device: int = 0):
     return info, pcost, perm
 
 
+ORDER_USES = ("launches", "lane_orders_made", "lane_order_uses", "work_orders_made", "work_order_uses",
+              "crawl_skips", "slots", "lane_block")
+
+
+def debug_order_uses(device: int = 0) -> dict:
+    """Test hook (vr_debug_order_uses): the device's monotonic launch counters as a dict --
+    launches, lane_orders_made, lane_order_uses, work_orders_made, work_order_uses,
+    crawl_skips, the ring's slots and lane_block = (width, height) in pixels.  Host state
+    only: no HIP call."""
+    raw = (ctypes.c_uint64 * 8)()
+    check(lib().vr_debug_order_uses(int(device), raw), "vr_debug_order_uses")
+    d = dict(zip(ORDER_USES, (int(x) for x in raw)))
+    d["lane_block"] = (d["lane_block"] >> 16, d["lane_block"] & 0xFFFF)
+    return d
+
+
 def render_tiles(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, lighting: _capi.VrLighting,
                  info: VoxelSceneInfo, width: int, height: int, band_rows: int, tile_cols: int, rank: int,
                  nranks: int, out: torch.Tensor, stream=None) -> torch.Tensor:
