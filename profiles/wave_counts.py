@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Wave-level execution counts of one frame from a VR_DIAG build
-(profiles/build_variant.sh diag -- -DVR_DIAG): how many times a wave ran each
-loop body and each per-walk / per-ray block.  Multiplied by the blocks' static
-VALU counts (profiles/loop_isa.py) this splits the kernel's SQ_INSTS_VALU into
-loop and non-loop work.
-  VR_LIBRARY=voxelraymarcher_amd/ab/libvr_diag.so python profiles/wave_counts.py [C2]"""
+"""Wave-level execution counts of one frame from the counting build, libvr_cover.so (the
+library's sources with -DVR_DIAG; `make -C voxelraymarcher_amd/csrc` builds it beside
+libvr.so): how many times a wave ran each loop body, each per-walk / per-ray block and each
+rarely-taken fallback block (32 and up: tests/cover_run.py GUARDS).  Multiplied by the
+blocks' static VALU counts (profiles/loop_isa.py) the loop counters split the kernel's
+SQ_INSTS_VALU into loop and non-loop work.
+  VR_LIBRARY=voxelraymarcher_amd/libvr_cover.so python profiles/wave_counts.py [C2]"""
 import ctypes
 import os
 import sys
@@ -27,6 +28,8 @@ NAMES = {0: "primary VCS walks (sign-specialised)", 1: "primary VCS walks (gener
          21: "longest-axis iterations with a jumping lane",
          22: "primary iterations, no lane skipping", 23: "primary iterations, every lane skipping",
          24: "shadow iterations, no lane skipping", 25: "shadow iterations, every lane skipping"}
+from tests.cover_run import GUARDS, N_COUNTERS  # noqa: E402
+NAMES.update({k: v[0] for k, v in GUARDS.items() if k >= 32})
 
 name = sys.argv[1] if len(sys.argv) > 1 else "C2"
 cfg = vr.CONFIGS[name]
@@ -38,13 +41,15 @@ lit = vr.setup_constant_values()
 info = vr.VoxelSceneInfo((0, 0, 0), cfg.scale)
 out = torch.empty(W * H, dtype=torch.int32, device="cuda")
 lib = _capi.lib()
-buf = (ctypes.c_ulonglong * 32)()
+lib.vr_diag_fetch.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]   # (no part of include/vr.h)
+lib.vr_diag_fetch.restype = ctypes.c_int
+buf = (ctypes.c_uint64 * N_COUNTERS)()
 vr.run_raymarching_kernel(scene, cfg.algorithm, cam, lit, info, W, H, out, kernel=vr.Kernel.TILE)
 assert lib.vr_diag_fetch(buf, 1) == 0
 vr.run_raymarching_kernel(scene, cfg.algorithm, cam, lit, info, W, H, out, kernel=vr.Kernel.TILE)
 assert lib.vr_diag_fetch(buf, 1) == 0
 waves = ((W + 7) // 8) * ((H + 7) // 8)
 print(f"{name} {W}x{H}: {waves} waves")
-for k in range(32):
+for k in range(N_COUNTERS):
     if buf[k]:
         print(f"  [{k:2d}] {NAMES.get(k, '?'):45s} {buf[k]:12d}  ({buf[k] / waves:8.2f} per wave)")

@@ -21,9 +21,15 @@
 #include <algorithm>
 #include <type_traits>
 
-// VR_DIAG (profiling builds only, profiles/wave_counts.py): wave-level execution
-// counters -- one atomic per wave per counted event, from the wave's first
-// active lane.  Never part of the library build.
+// VR_DIAG (the counting build libvr_cover.so; profiles/wave_counts.py and
+// tests/cover_run.py read it): wave-level execution counters -- one atomic per wave
+// per counted event, from the wave's first active lane.  Never part of libvr.so.
+// 0-25: the hot loops (profiles/wave_counts.py NAMES).  32-58: the rarely-taken blocks
+// that keep the walks exact -- one beside every __builtin_expect site, the ray
+// direction's fallback, every sign-pattern arm (VR_DIAG_PAT: primary 43 + pattern,
+// shadow 51 + pattern), a wave's second pattern pass, pattern 7 through P,P,P --
+// whose reach tests/test_gpu_edges.py::test_guards_are_reached proves (the table
+// GUARDS of tests/cover_run.py names every index).
 #ifdef VR_CRAWL_PROF
 // per crawl record of the last crawl pass (profiles/crawl_prof.py): {shader cycles, plain
 // loop iterations (bit 31: walked from the start), crawl_run calls that applied steps, their
@@ -31,7 +37,7 @@
 __device__ unsigned int g_vr_crawl_prof[16384 * 8];
 #endif
 #ifdef VR_DIAG
-__device__ unsigned long long g_vr_diag[32];
+__device__ unsigned long long g_vr_diag[64];
 #define VR_DIAG_COUNT(k)                                                              \
     do {                                                                             \
         if (__lane_id() == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) \
@@ -41,9 +47,11 @@ __device__ unsigned long long g_vr_diag[32];
     do {                                                       \
         if (__builtin_amdgcn_ballot_w64(c) != 0) VR_DIAG_COUNT(k); \
     } while (0)
+#define VR_DIAG_PAT(shadow, p) VR_DIAG_COUNT(((shadow) ? 51 : 43) + (p))
 #else
 #define VR_DIAG_COUNT(k) do { } while (0)
 #define VR_DIAG_COUNT_IF(c, k) do { } while (0)
+#define VR_DIAG_PAT(shadow, p) do { } while (0)
 #endif
 
 namespace vr {
@@ -304,6 +312,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                               fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= 0x1p-90f;
             tX = div_fast(ax, r0x); tY = div_fast(ay, r0y); tZ = div_fast(az, r0z);
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0, 0)) {
+                VR_DIAG_COUNT(32);                     // initial step: a lane outside div_fast's domain
                 tX = fast ? tX : (zx ? kInf : ax / d.x);
                 tY = fast ? tY : (zy ? kInf : ay / d.y);
                 tZ = fast ? tZ : (zz ? kInf : az / d.z);
@@ -487,6 +496,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                 if (chk) {
                                     const bool bad = !(am >= nlim);
                                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+                                        VR_DIAG_COUNT(33);     // VCS walk, one divisor: IEEE fallback
                                         sMin = bad ? am / fabsf(d.x) : sMin;
                                         crawl = bad & walk_ok & skip & (sMin == 0.0f) &
                                                 (CRAWL ? ic + 1u - (0x42800000u - kBudget) >= crawl_after : !crawl_off);
@@ -498,6 +508,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                 if (chk) {
                                     const bool bad = !(fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= nlim);
                                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+                                        VR_DIAG_COUNT(34);     // VCS walk, three divisors: IEEE fallback
                                         sX = bad ? (zx ? kInf : ax / d.x) : sX;
                                         sY = bad ? (zy ? kInf : ay / d.y) : sY;
                                         sZ = bad ? (zz ? kInf : az / d.z) : sZ;
@@ -539,22 +550,33 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                         // VGPRs against the specialised loops' ~72 (7 waves/SIMD).  (An
                         // equal-component shadow direction has pattern 0 or 7.)
                         bool todo = true;
+#ifdef VR_DIAG
+                        uint32_t pass = 0;
+#endif
                         while (todo) {
                             const uint32_t pat = __builtin_amdgcn_readfirstlane(sg);
+#ifdef VR_DIAG
+                            if (++pass == 2u) VR_DIAG_COUNT(41);   // this wave runs a second pattern pass
+#endif
                             if (sg == pat) {
                                 todo = false;
                                 switch (pat) {
-                                case 0: walk(N{}, N{}, N{}); break;
+                                case 0: VR_DIAG_PAT(SHADOW, 0); walk(N{}, N{}, N{}); break;
                                 case 7:
-                                    if (__builtin_amdgcn_ballot_w64(!walk_ok) == 0) walk(Sgn<2>{}, Sgn<2>{}, Sgn<2>{});
-                                    else walk(P{}, P{}, P{});
+                                    VR_DIAG_PAT(SHADOW, 7);
+                                    if (__builtin_amdgcn_ballot_w64(!walk_ok) == 0) {
+                                        walk(Sgn<2>{}, Sgn<2>{}, Sgn<2>{});
+                                    } else {
+                                        VR_DIAG_COUNT(42);         // a lane's walk_ok failed: P,P,P with checks
+                                        walk(P{}, P{}, P{});
+                                    }
                                     break;
-                                case 1: if (!EQ) walk(P{}, N{}, N{}); break;
-                                case 2: if (!EQ) walk(N{}, P{}, N{}); break;
-                                case 3: if (!EQ) walk(P{}, P{}, N{}); break;
-                                case 4: if (!EQ) walk(N{}, N{}, P{}); break;
-                                case 5: if (!EQ) walk(P{}, N{}, P{}); break;
-                                default: if (!EQ) walk(N{}, P{}, P{}); break;
+                                case 1: VR_DIAG_PAT(SHADOW, 1); if (!EQ) walk(P{}, N{}, N{}); break;
+                                case 2: VR_DIAG_PAT(SHADOW, 2); if (!EQ) walk(N{}, P{}, N{}); break;
+                                case 3: VR_DIAG_PAT(SHADOW, 3); if (!EQ) walk(P{}, P{}, N{}); break;
+                                case 4: VR_DIAG_PAT(SHADOW, 4); if (!EQ) walk(N{}, N{}, P{}); break;
+                                case 5: VR_DIAG_PAT(SHADOW, 5); if (!EQ) walk(P{}, N{}, P{}); break;
+                                default: VR_DIAG_PAT(SHADOW, 6); if (!EQ) walk(N{}, P{}, P{}); break;
                                 }
                             }
                         }
@@ -670,7 +692,10 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                     float sMin = div_fast(am, rx);
                     if (!okw) {
                         const bool bad = !(am >= nlim);
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) sMin = bad ? am / fabsf(d.x) : sMin;
+                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+                            VR_DIAG_COUNT(35);             // cuckoo walk, one divisor: IEEE fallback
+                            sMin = bad ? am / fabsf(d.x) : sMin;
+                        }
                     }
                     return sMin;
                 }
@@ -678,6 +703,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                 if (!okw) {
                     const bool bad = !(fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= nlim);
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+                        VR_DIAG_COUNT(36);                 // cuckoo walk, three divisors: IEEE fallback
                         sX = bad ? (zx ? kInf : ax / d.x) : sX;
                         sY = bad ? (zy ? kInf : ay / d.y) : sY;
                         sZ = bad ? (zz ? kInf : az / d.z) : sZ;
@@ -1018,11 +1044,26 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                 ++it;                                // tick()
                 ex = it > kBudget ? kOver : kGo;
                 // performVoxelSpaceJump's cluster skip (:707-725), integer planes from g:
-                // d > 0 ? ((g / 8) + 1) * 8 : (g / 8) * 8.  (g / 8) * 8 is g & ~7 for g >= 0
-                // (a walk's cells never go below 0; the C division form for any wave
-                // holding a negative one)
+                // d > 0 ? ((g / 8) + 1) * 8 : (g / 8) * 8.  (g / 8) * 8 is g & ~7 for g >= 0; the
+                // C division form below is for a wave holding a negative cell, and no finite
+                // input gives one (counter 37 stays 0; tests/cover_run.py UNREACHABLE):
+                //  - a jump goes on from the cell it landed in only if that cell is in the region
+                //    (else kLeft ends the walk above), so a negative g would have to be the cell of
+                //    the probe that started the jump: slot A, B or C;
+                //  - a slot's coordinates are g's or C's = g + a.  C is in the region (else kTail
+                //    ended the loop), so a negative coordinate would have to be g's own, and g is
+                //    a slot or a landing cell of an earlier iteration -- in the region by the same
+                //    argument -- or the walk's first cell f2i(o);
+                //  - the walk starts at o = so - 64 * floor(so / 64) >= 0 (primary, advance_region:
+                //    the same form after a region is left), or, a shadow walk, at the primary hit's
+                //    location, on a face of a voxel of the region: o > -1 on every axis, and f2i
+                //    truncates towards zero, so the first cell is >= 0.  (It can be 64,
+                //    from o = 64.0 exactly: the probes outside the region that the alias fixture
+                //    reaches, counter 38, are all on that side.)
+                // Tried on the CPU: tests/test_edge_cases.py::test_no_jump_starts_in_a_negative_cell.
                 int32_t bL = gL & ~7, bM = gM & ~7, bS = gS & ~7;
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64((gL | gM | gS) < 0) != 0, 0)) {
+                    VR_DIAG_COUNT(37);                 // a jumping lane stands in a negative cell
                     bL = (gL / 8) * 8; bM = (gM / 8) * 8; bS = (gS / 8) * 8;
                 }
                 const int32_t nL = bL + offL, nM = bM + offM, nS = bS + offS;
@@ -1109,6 +1150,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                 }
             }
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!inr) != 0, 0)) {
+                VR_DIAG_COUNT(38);                     // a probe slot outside the region: the aliasing form
                 if (!inr) {
                     stop = 3u; hit = false; col = kEmpty;
                     const i3 P[3] = {to_i3(gL, AM, AS), to_i3(gL, CM, CS), to_i3(CL, CM, CS)};
@@ -1291,6 +1333,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                               (__float_as_uint(ay) == 0u || div_fast_ok(ay, rc[1])) &&
                               (__float_as_uint(az) == 0u || div_fast_ok(az, rc[2]));
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0, 0)) {
+                VR_DIAG_COUNT(39);                     // entry clip: a lane outside div_fast's domain
                 tX = fast ? tX : ax / d.x;
                 tY = fast ? tY : ay / d.y;
                 tZ = fast ? tZ : az / d.z;
@@ -1427,6 +1470,7 @@ __device__ __forceinline__ bool pixel_ray(const KView& v, uint32_t x, uint32_t l
     const Rcp rl = rcp_setup(len);
     auto okn = [&](float n) { return __float_as_uint(n) == 0u || div_fast_ok(n, rl); };
     rd = f3{div_fast(c.x, rl), div_fast(c.y, rl), div_fast(c.z, rl)};
+    VR_DIAG_COUNT_IF(!(okn(c.x) && okn(c.y) && okn(c.z)), 40);   // ray direction: IEEE fallback
     if (!(okn(c.x) && okn(c.y) && okn(c.z))) rd = f3{c.x / len, c.y / len, c.z / len};
     return true;
 }
@@ -2188,11 +2232,14 @@ extern "C" int vr_crawl_prof_fetch(unsigned int* out, unsigned int n) {
 }
 #endif
 #ifdef VR_DIAG
-extern "C" int vr_diag_fetch(unsigned long long* out, int reset) {
+// The 64 counters (the device the calling thread has current), optionally zeroed after the
+// read.  Only the counting build has it: it is no part of include/vr.h.
+extern "C" int vr_diag_fetch(uint64_t* out, int reset) {
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counter width");
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vr_diag), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vr_diag), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
     if (reset) {
-        unsigned long long z[32] = {0};
+        unsigned long long z[64] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_vr_diag), z, sizeof z) != hipSuccess) return -1;
     }
     return 0;
