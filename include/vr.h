@@ -225,6 +225,78 @@ int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam,
             const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
             vr_hit* hits, int outputs_on_device, void* stream);
 
+/* One ray of vr_trace. */
+typedef struct {            /* 32 bytes, 16-byte aligned records: two 16-byte loads */
+    float    origin[3];     /* world space, as a camera's ray origin */
+    uint32_t reserved0;     /* write 0; not read */
+    float    direction[3];  /* world space, any length: the walk uses makeUnitVector(direction) */
+    uint32_t reserved1;     /* write 0; not read */
+} vr_ray;
+
+/* Which lane walks which ray of a vr_trace call.  The records never depend on it.
+ * AUTO is GIVEN for every n: measured on C2 and C4 at 1920x1080 with 4096 to 2 073 600 rays
+ * (tile-order, shuffled and bounce rays; key kernel and sort included; this change on top of
+ * fb3c0b6, profiles/trace/README.md), COHERENT won at no size -- the sort costs more than the
+ * incoherence it removes (2 073 600 shuffled C2 rays: 0.457 ms GIVEN, 0.697 ms COHERENT).  The
+ * mode stays: it is exact and tested, and a caller whose rays are worse than a shuffle can
+ * ask for it. */
+typedef enum {
+    VR_TRACE_ORDER_AUTO = 0,      /* the library's measured choice: GIVEN */
+    VR_TRACE_ORDER_GIVEN = 1,     /* lane i of the launch walks ray i */
+    VR_TRACE_ORDER_COHERENT = 2   /* rays sorted on the device by direction signs, origin cell and direction */
+} vr_trace_order;
+
+/* Closest-hit queries for arbitrary rays: hits[i] is the primary hit of rays[i], the record
+ * vr_pick writes (status VR_HIT_MISS, VR_HIT_VOXEL or VR_HIT_NEVER, never VR_HIT_OUTSIDE; every
+ * other field 0 unless VOXEL; voxel, color, normal, region and point as for vr_pick).  The walk
+ * is rayMarchVoxelScene / rayMarchVoxelSceneLongestAxis from world origin rays[i].origin in
+ * direction d / sqrtf(d.x*d.x + d.y*d.y + d.z*d.z), d = rays[i].direction (makeUnitVector,
+ * Vector3.cuh:162-165: correctly rounded sqrt and divisions); the scene-space origin is
+ * (origin - translation) * scale, as in a render.
+ *
+ * No ray is rejected.  A zero, NaN or infinite direction or origin gives the record the
+ * reference's walk gives for it (a zero direction normalises to NaN; from inside the scene the
+ * original walk then never finishes: VR_HIT_NEVER): no status is promised for such rays, only
+ * that the record equals the reference's.
+ *
+ * order (vr_trace_order) decides only the execution order: the records are byte for byte the
+ * same under every order and hits[i] always belongs to rays[i].  COHERENT computes a 64-bit key
+ * per ray and sorts (key, index) on the device; its scratch (12 bytes per ray for keys and
+ * indices, twice, plus the sort's temporary) is allocated on the scene's device for the call
+ * and released before it returns.
+ *
+ * rays: n records, on the scene's device (16-byte aligned) when inputs_on_device != 0; hits: n
+ * records, on the device (16-byte aligned) when outputs_on_device != 0.  Host arrays are
+ * staged through device buffers the call allocates and frees; GIVEN with everything on the
+ * device allocates nothing.  The work runs on `stream` and the call returns when hits[0..n) are
+ * written.  n == 0 returns VR_OK and does nothing.  As a pick, a trace is not a render launch:
+ * no ring slot, nothing learned or forgotten.
+ *
+ * VR_E_INVALID (nothing is written to hits): s or translation NULL; rays or hits NULL with
+ * n > 0; n >= 2^31; an unknown algorithm; an unknown order; a misaligned device array; a
+ * stream that is capturing a HIP graph. */
+int vr_trace(const vr_scene* s, vr_algo algo, const float translation[3], uint32_t scale,
+             const vr_ray* rays, size_t n, int inputs_on_device,
+             vr_hit* hits, int outputs_on_device, uint32_t order, void* stream);
+
+/* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
+ * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
+ * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the
+ * very division the render applies, so vr_trace(vr_camera_rays(px, py)) is byte-identical to
+ * vr_pick(px, py) for every pixel inside the frame.  A pixel with px >= width or py >= height
+ * gets a ray whose six floats are the quiet NaN 0x7FC00000.  reserved0 and reserved1 are
+ * written as 0.
+ *
+ * Runs on `device` (no scene is needed) as one small kernel on `stream`; px, py and rays are
+ * host arrays, or device arrays (rays 16-byte aligned) when the flags say so, staged as
+ * vr_pick stages them; returns when rays[0..n) are written.  n == 0 returns VR_OK.
+ *
+ * VR_E_INVALID: cam NULL; px, py or rays NULL with n > 0; width or height outside 1..65536;
+ * n >= 2^31; device outside 0..63 or not present; a stream that is capturing a HIP graph. */
+int vr_camera_rays(int device, const vr_camera* cam, uint32_t width, uint32_t height,
+                   const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
+                   vr_ray* rays, int outputs_on_device, void* stream);
+
 /* rayMarchSceneOriginal / rayMarchSceneJumpAxis (Renderer.cuh:1033-1063) as
  * launched by runRaymarchingKernel (Main.cu:105-163), for image rows
  * [row_begin, row_end) of a width x height frame.  out_dev: device buffer of

@@ -158,4 +158,29 @@ inline std::vector<vr_hit> pick(uint32_t width, uint32_t height, RayMarchAlgorit
     return hits;
 }
 
+// vr_trace: the closest hit of each ray (any origin, any direction length), as vr_hit records --
+// what pick() gives for a pixel, for rays that are no pixel of a camera.  Host arrays in, host
+// records out; returns when they are written.  The order never changes a record.
+inline std::vector<vr_hit> trace(RayMarchAlgorithm algo, const VoxelSceneInfo& info, const DeviceScene& scene,
+                                 const std::vector<vr_ray>& rays, vr_trace_order order = VR_TRACE_ORDER_AUTO,
+                                 void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<vr_hit> hits(rays.size());
+    check(vr_trace(scene.get(), (vr_algo)algo, t, info.scale, rays.data(), rays.size(), 0, hits.data(), 0, (uint32_t)order,
+                   stream),
+          "trace");
+    return hits;
+}
+
+// vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
+// frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
+inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,
+                                       const std::vector<uint32_t>& py, int device = 0, void* stream = nullptr) {
+    if (px.size() != py.size()) throw Error(VR_E_INVALID, "camera_rays: px and py lengths differ");
+    std::vector<vr_ray> rays(px.size());
+    check(vr_camera_rays(device, &camera.raw(), width, height, px.data(), py.data(), px.size(), 0, rays.data(), 0, stream),
+          "camera_rays");
+    return rays;
+}
+
 }  // namespace vrx

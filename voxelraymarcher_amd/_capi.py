@@ -72,6 +72,13 @@ class VrHit(ctypes.Structure):
                 ("region", c_int32 * 3), ("point", c_float * 3), ("reserved", c_uint32 * 2)]
 
 
+class VrRay(ctypes.Structure):
+    """vr_ray: one ray of vr_trace (32 bytes)."""
+    _fields_ = [("origin", c_float * 3), ("reserved0", c_uint32), ("direction", c_float * 3), ("reserved1", c_uint32)]
+
+
+VR_TRACE_ORDER_AUTO, VR_TRACE_ORDER_GIVEN, VR_TRACE_ORDER_COHERENT = 0, 1, 2
+
 
 class VrError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str):
@@ -119,6 +126,10 @@ SIGNATURES = {
                                 c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
     "vr_pick": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(c_float), c_uint32, c_uint32, c_uint32, c_void_p,
                         c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "vr_trace": (c_int, [c_void_p, c_int, POINTER(c_float), c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                         c_uint32, c_void_p]),
+    "vr_camera_rays": (c_int, [c_int, POINTER(VrCamera), c_uint32, c_uint32, c_void_p, c_void_p, c_size_t, c_int,
+                               c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
     "vr_synth_generate": (c_int, [POINTER(VrSynthParams), POINTER(c_int32), POINTER(c_uint32), c_size_t,
                                   POINTER(c_size_t)]),
@@ -163,6 +174,7 @@ __all__ = ["lib", "check", "VrCamera", "VrLighting", "VrRenderOpts", "VR_RENDER_
            "VR_KERNEL_TILE", "VR_KERNEL_TILE_REWALK", "VR_SCHEDULE_AUTO", "VR_SCHEDULE_GRID",
            "VR_SCHEDULE_HEAVIEST_FIRST", "VR_OCCUPANCY_AUTO", "VR_OCCUPANCY_LONE", "VR_OCCUPANCY_IN_FLIGHT",
            "VrSceneInfo", "VrSynthParams", "VrHit", "VR_HIT_MISS",
-           "VR_HIT_VOXEL", "VR_HIT_NEVER", "VR_HIT_OUTSIDE", "VrError", "SIGNATURES",
+           "VR_HIT_VOXEL", "VR_HIT_NEVER", "VR_HIT_OUTSIDE", "VrRay", "VR_TRACE_ORDER_AUTO",
+           "VR_TRACE_ORDER_GIVEN", "VR_TRACE_ORDER_COHERENT", "VrError", "SIGNATURES",
            "VR_STORE_VCS", "VR_STORE_HASHTABLE", "VR_ALGO_LONGESTAXIS", "VR_ALGO_ORIGINAL", "f3", "LIB_PATH",
            "c_uint8"]

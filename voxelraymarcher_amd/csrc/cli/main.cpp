@@ -12,6 +12,10 @@
 //                   [--pick X,Y]...  (after the frame is rendered: one line per pick with the
 //                                 voxel, stored colour and shading normal behind pixel (X, Y),
 //                                 y = 0 the top row -- vr_pick; not with --gpus N > 1)
+//                   [--trace OX,OY,OZ,DX,DY,DZ]...  (beside the picks: one line per ray with the
+//                                 voxel, colour, normal and hit point it reaches from world origin
+//                                 O in direction D (any length) -- vr_trace, with the scale above
+//                                 and a zero translation; not with --gpus N > 1)
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -44,6 +48,23 @@ bool parse_vec3(const char* s, float out[3]) {
             ++s;
         }
     }
+    return *s == 0;
+}
+
+// "ox,oy,oz,dx,dy,dz" -> a vr_ray; false on malformed input.
+bool parse_ray(const char* s, vr_ray& ray) {
+    float f[6];
+    char* end = nullptr;
+    for (int i = 0; i < 6; ++i) {
+        f[i] = std::strtof(s, &end);
+        if (end == s) return false;
+        s = end;
+        if (i < 5) {
+            if (*s != ',') return false;
+            ++s;
+        }
+    }
+    ray = vr_ray{{f[0], f[1], f[2]}, 0u, {f[3], f[4], f[5]}, 0u};
     return *s == 0;
 }
 
@@ -93,6 +114,7 @@ int main(int argc, char* argv[]) {
     bool multi = false;                      // --gpus given: the RCCL-tiled frame
     bool shadows = true, point_light = false, has_dir = false;
     std::vector<uint32_t> pick_x, pick_y;    // --pick X,Y (repeatable)
+    std::vector<vr_ray> trace_rays;          // --trace OX,OY,OZ,DX,DY,DZ (repeatable)
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -126,11 +148,19 @@ int main(int argc, char* argv[]) {
             pick_x.push_back(x);
             pick_y.push_back(y);
         }
+        else if (a == "--trace") {
+            vr_ray ray;
+            if (!parse_ray(next("--trace"), ray)) {
+                std::cerr << "--trace needs OX,OY,OZ,DX,DY,DZ" << std::endl;
+                std::exit(2);
+            }
+            trace_rays.push_back(ray);
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
-                         "[--pick X,Y]..." << std::endl;
+                         "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]..." << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -146,6 +176,10 @@ int main(int argc, char* argv[]) {
     }
     if (!pick_x.empty() && multi && gpus > 1) {
         std::cerr << "ERROR: --pick is a single-GPU query: not with --gpus " << gpus << std::endl;
+        return 2;
+    }
+    if (!trace_rays.empty() && multi && gpus > 1) {
+        std::cerr << "ERROR: --trace is a single-GPU query: not with --gpus " << gpus << std::endl;
         return 2;
     }
     // argv[1] = scale (Main.cu:181-186); optional here (README.md:22-25 omits it).
@@ -215,6 +249,21 @@ int main(int argc, char* argv[]) {
         lit.use_point_light = point_light;                       // Main.cu:37
         lit.use_shadows = shadows;                               // Main.cu:40
 
+        // --trace: the closest hit of each given ray (vr_trace), printed after the picks
+        auto print_traces = [&]() {
+            if (trace_rays.empty()) return;
+            const std::vector<vr_hit> hits = vrx::trace(algo, sinfo, scene, trace_rays);
+            for (size_t i = 0; i < hits.size(); ++i) {
+                const vr_hit& h = hits[i];
+                if (h.status == VR_HIT_VOXEL)
+                    std::printf("trace %zu voxel %d %d %d color 0x%06X normal %d %d %d point %.9g %.9g %.9g\n", i, h.voxel[0],
+                                h.voxel[1], h.voxel[2], h.color, h.normal[0], h.normal[1], h.normal[2], h.point[0],
+                                h.point[1], h.point[2]);
+                else
+                    std::printf("trace %zu %s\n", i, h.status == VR_HIT_MISS ? "miss" : "never");
+            }
+            std::fflush(stdout);
+        };
         // --pick: the hit each picked pixel of the rendered frame was shaded from (vr_pick)
         auto print_picks = [&]() {
             if (pick_x.empty()) return;
@@ -254,6 +303,7 @@ int main(int argc, char* argv[]) {
                 std::cout << "  rank " << i << " render " << (long long)(best.rank_render_ms[i] * 1000.0f)
                           << " microseconds" << std::endl;
             print_picks();                   // (--gpus 1: the scene of this process's device)
+            print_traces();
             std::vector<uint8_t> host;
             if (!mg.download(host)) {
                 std::cerr << "ERROR: " << mg.error() << std::endl;
@@ -287,6 +337,7 @@ int main(int argc, char* argv[]) {
         std::cout << "Execution Time for Ray Marching Algorithm is: " << (long long)(best_ms * 1000.0f)
                   << " microseconds (" << (double)width * height / (best_ms * 1e3) << " Mrays/s)" << std::endl;
         print_picks();
+        print_traces();
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,
         // async copy into pinned memory, parallel PNG encode (vr_png_write).
         const size_t nbytes = (size_t)width * height * 3;

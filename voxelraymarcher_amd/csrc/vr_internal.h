@@ -191,6 +191,23 @@ uint32_t crawl_grid(uint32_t records, uint32_t rpw);
 constexpr uint32_t kPickMiss = 0, kPickVoxel = 1, kPickNever = 2, kPickOutside = 3;   // = VR_HIT_*
 hipError_t launch_pick(int store, int algo, const KScene& s, const KView& v, const uint32_t* px, const uint32_t* py,
                        uint32_t n, void* hits, hipStream_t stream);
+// vr_trace's kernel: the primary hit of each of n rays (32-byte vr_ray records, 16-byte aligned
+// device memory) as vr_hit records, one lane per ray with the pick's walker.  idx (or null):
+// lane i walks ray idx[i] and writes record idx[i]; it must be a permutation of 0..n-1.  Of the
+// view only translation and scale_f are read.
+hipError_t launch_trace(int store, int algo, const KScene& s, const KView& v, const void* rays, const uint32_t* idx,
+                        uint32_t n, void* hits, hipStream_t stream);
+// vr_camera_rays' kernel: the rays of pixels (px[i], py[i]) of the view's frame (one band over it).
+hipError_t launch_camera_rays(const KView& v, const uint32_t* px, const uint32_t* py, uint32_t n, void* rays,
+                              hipStream_t stream);
+// The coherent order of n rays (vr_trace.hip): a key per ray -- direction signs, the Morton code
+// of the origin's 8-voxel cell clamped to the scene's frame, the direction's cube-map cell -- and
+// a stable radix sort of (key, index).  *scratch is one hipMalloc on the current device that
+// holds the keys, the indices and the sort's temporary; *idx points into it at the sorted
+// indices.  The caller frees *scratch once the work queued on `stream` is done (on failure it is
+// already freed and null).
+hipError_t trace_order(const KScene& s, const KView& v, const void* rays, uint32_t n, hipStream_t stream,
+                       void** scratch, const uint32_t** idx);
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);
 // ht_filter of a cuckoo scene from its tables (one workgroup per region).

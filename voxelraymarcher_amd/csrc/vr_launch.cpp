@@ -1,6 +1,7 @@
 // vr_launch.cpp -- the render launch: the per-device slot ring, the learned orders and the
 // crawl-pass skip kept per slot (their decisions: vr_launch_plan.h), and the render entry
-// points of include/vr.h; vr_pick, which shares the view but none of the launch state.
+// points of include/vr.h; vr_pick, which shares the view but none of the launch state, and
+// vr_trace / vr_camera_rays, which share neither.
 //
 // Replaces runRaymarchingKernel (main/Main.cu:105-163).
 #include <algorithm>
@@ -639,6 +640,136 @@ int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam, const float t
     if (e == hipSuccess) e = es;
     release();
     if (e != hipSuccess) return hip_fail(e, "vr_pick");
+    return VR_OK;
+}
+
+// The closest hit of arbitrary rays (vr.h).  As vr_pick: not a render launch, nothing the render
+// path keeps per device is touched.  Every argument check comes before any device work.
+int vr_trace(const vr_scene* s, vr_algo algo, const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
+             int inputs_on_device, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream) {
+    static_assert(sizeof(vr_ray) == 32 && offsetof(vr_ray, reserved0) == 12 && offsetof(vr_ray, direction) == 16 &&
+                      offsetof(vr_ray, reserved1) == 28, "vr_ray: the record trace_kernel loads");
+    if (!s) return fail(VR_E_INVALID, "vr_trace: scene is NULL");
+    if (!translation) return fail(VR_E_INVALID, "vr_trace: translation NULL");
+    if (n && (!rays || !hits)) return fail(VR_E_INVALID, "vr_trace: rays/hits NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_trace: too many rays");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_trace: unknown algorithm");
+    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
+        return fail(VR_E_INVALID, "vr_trace: unknown order");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_trace: device rays must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_trace: device hits must be 16-byte aligned");
+    // the walk reads the view's translation and scale only (no camera, no light, no frame)
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
+    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
+    // AUTO is GIVEN at every n: COHERENT won at no measured size (vr.h, profiles/trace/README.md)
+    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(VR_E_INVALID, "vr_trace cannot be captured into a HIP graph (stream is capturing)");
+    void *tr = nullptr, *th = nullptr, *to = nullptr;     // owned by this call: rays, hits, the order's scratch
+    auto release = [&]() {
+        if (tr) (void)hipFree(tr);
+        if (th) (void)hipFree(th);
+        if (to) (void)hipFree(to);
+    };
+    const void* dr = rays;
+    if (!inputs_on_device) {
+        e = hipMalloc(&tr, n * sizeof(vr_ray));
+        if (e == hipSuccess) e = hipMemcpyAsync(tr, rays, n * sizeof(vr_ray), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_trace: ray upload"); }
+        dr = tr;
+    }
+    void* dh = hits;
+    if (!outputs_on_device) {
+        e = hipMalloc(&th, n * sizeof(vr_hit));
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_trace: hit buffer"); }
+        dh = th;
+    }
+    const uint32_t* idx = nullptr;
+    if (coherent) e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &to, &idx);
+    if (e == hipSuccess) e = vr::launch_trace((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, dh, st);
+    if (e == hipSuccess && !outputs_on_device)
+        e = hipMemcpyAsync(hits, th, n * sizeof(vr_hit), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    release();
+    if (e != hipSuccess) return hip_fail(e, "vr_trace");
+    return VR_OK;
+}
+
+// The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.
+int vr_camera_rays(int device, const vr_camera* cam, uint32_t width, uint32_t height, const uint32_t* px,
+                   const uint32_t* py, size_t n, int inputs_on_device, vr_ray* rays, int outputs_on_device, void* stream) {
+    if (!cam) return fail(VR_E_INVALID, "vr_camera_rays: camera NULL");
+    if (n && (!px || !py || !rays)) return fail(VR_E_INVALID, "vr_camera_rays: px/py/rays NULL");
+    if (width == 0 || height == 0 || width > 65536 || height > 65536)
+        return fail(VR_E_INVALID, "vr_camera_rays: bad image size");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_camera_rays: too many pixels");
+    if (device < 0 || device > 63) return fail(VR_E_INVALID, "vr_camera_rays: bad device");
+    if (n == 0) return VR_OK;
+    if (outputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_camera_rays: device rays must be 16-byte aligned");
+    // the view of a whole-frame render: one band, rank 0 of 1 (as vr_pick's); only the camera is read
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) {
+        v.llc[i] = cam->lower_left[i]; v.hor[i] = cam->horizontal[i]; v.ver[i] = cam->vertical[i];
+        v.org[i] = cam->origin[i];
+    }
+    v.W = width;
+    v.H = height;
+    v.LW = width;
+    v.row_limit = height;
+    v.band_rows = height;
+    v.band_minv = height == 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / height);
+    v.nranks = 1;
+    v.local_rows = height;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(VR_E_INVALID, "vr_camera_rays: no such device");
+    DeviceGuard dg(device);
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(VR_E_INVALID, "vr_camera_rays cannot be captured into a HIP graph (stream is capturing)");
+    const uint32_t *dpx = px, *dpy = py;
+    void *tq = nullptr, *tr = nullptr;      // staging owned by this call: {px, py}, rays
+    auto release = [&]() {
+        if (tq) (void)hipFree(tq);
+        if (tr) (void)hipFree(tr);
+    };
+    if (!inputs_on_device) {
+        e = hipMalloc(&tq, 2 * n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(tq, px, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((uint32_t*)tq + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_camera_rays: pixel upload"); }
+        dpx = (const uint32_t*)tq;
+        dpy = dpx + n;
+    }
+    void* dr = rays;
+    if (!outputs_on_device) {
+        e = hipMalloc(&tr, n * sizeof(vr_ray));
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_camera_rays: ray buffer"); }
+        dr = tr;
+    }
+    e = vr::launch_camera_rays(v, dpx, dpy, (uint32_t)n, dr, st);
+    if (e == hipSuccess && !outputs_on_device)
+        e = hipMemcpyAsync(rays, tr, n * sizeof(vr_ray), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    release();
+    if (e != hipSuccess) return hip_fail(e, "vr_camera_rays");
     return VR_OK;
 }
 

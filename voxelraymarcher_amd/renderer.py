@@ -170,6 +170,10 @@ class DeviceScene:
         """vr_pick with this scene: see pick()."""
         return pick(self, algorithm, camera, info, width, height, px, py, stream=stream)
 
+    def trace(self, algorithm, info, rays, order=None, stream=None):
+        """vr_trace with this scene: see trace()."""
+        return trace(self, algorithm, info, rays, order=TraceOrder.AUTO if order is None else order, stream=stream)
+
     def close(self) -> None:
         if self._h:
             lib().vr_scene_destroy(self._h)
@@ -503,6 +507,103 @@ def pick(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info:
         check(lib().vr_pick(*args, px.ctypes.data_as(c_void_p), py.ctypes.data_as(c_void_p), n, 0,
                             hits.ctypes.data_as(c_void_p), 0, sp), "vr_pick")
     return hits
+
+
+class TraceOrder(enum.IntEnum):
+    """vr_trace_order: which lane walks which ray (the records never depend on it)."""
+    AUTO = _capi.VR_TRACE_ORDER_AUTO            # the library's measured choice (include/vr.h)
+    GIVEN = _capi.VR_TRACE_ORDER_GIVEN          # lane i walks ray i
+    COHERENT = _capi.VR_TRACE_ORDER_COHERENT    # rays sorted on the device by direction and origin cell
+
+
+# vr_ray, field for field (32 bytes)
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("reserved0", "<u4"), ("direction", "<f4", (3,)), ("reserved1", "<u4")])
+assert RAY_DTYPE.itemsize == ctypes.sizeof(_capi.VrRay) == 32
+
+
+def _rays_numpy(rays) -> np.ndarray:
+    """A RAY_DTYPE array from a RAY_DTYPE array or an (n, 6) array of origin and direction."""
+    if isinstance(rays, np.ndarray) and rays.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(rays).reshape(-1)
+    a = np.asarray(rays, dtype=np.float32)
+    if a.size == 0:
+        return np.zeros(0, dtype=RAY_DTYPE)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("rays must be a RAY_DTYPE array or an (n, 6) array: origin, direction")
+    out = np.zeros(a.shape[0], dtype=RAY_DTYPE)
+    out["origin"], out["direction"] = a[:, :3], a[:, 3:]
+    return out
+
+
+def trace(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, rays,
+          order: TraceOrder = TraceOrder.AUTO, stream=None):
+    """vr_trace: the closest hit of each ray -- the record pick() gives for a pixel, for rays that
+    are no pixel of a camera.  The walk starts at the world-space `origin` and runs along
+    direction / |direction| (any length); info gives the translation and scale, as for a render.
+    A numpy RAY_DTYPE array, or an (n, 6) float array of origin and direction, gives a numpy
+    HIT_DTYPE array; a CUDA float32 tensor on the scene's device -- (n, 8), the bytes of vr_ray,
+    or (n, 6) -- gives an (n, 16) int32 CUDA tensor of the records' bytes.  `order` changes the
+    execution order only, never a record.  A zero, NaN or infinite ray gets the record the
+    reference's walk gives it.  Runs on `stream` (default: the current stream) and returns when
+    the records are written."""
+    sp = _stream_ptr(stream)
+    args = (scene.handle, int(algorithm), f3(info.translation), int(info.scale))
+    if hasattr(rays, "is_cuda") and rays.is_cuda:
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] not in (6, 8):
+            raise TypeError("rays must be a float32 CUDA tensor of shape (n, 8) or (n, 6)")
+        if rays.shape[1] == 6:
+            full = torch.zeros((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+            full[:, 0:3], full[:, 4:7] = rays[:, 0:3], rays[:, 3:6]
+            rays = full
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        hits = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
+        if n:
+            check(lib().vr_trace(*args, c_void_p(rays.data_ptr()), n, 1, c_void_p(hits.data_ptr()), 1, int(order), sp),
+                  "vr_trace")
+        return hits
+    rays = _rays_numpy(rays)
+    n = rays.shape[0]
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    if n:
+        check(lib().vr_trace(*args, rays.ctypes.data_as(c_void_p), n, 0, hits.ctypes.data_as(c_void_p), 0, int(order),
+                             sp), "vr_trace")
+    return hits
+
+
+def camera_rays(camera: Camera, width: int, height: int, px, py, device: int = 0, stream=None):
+    """vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
+    frame (y = 0 is the top row): origin on the image plane, direction origin - eye, not
+    normalised, so trace(camera_rays(px, py)) has the bytes of pick(px, py) for pixels inside the
+    frame; a pixel outside it gets an all-NaN ray.  numpy (or list) px/py give a numpy RAY_DTYPE
+    array; CUDA int32/uint32 tensors give an (n, 8) float32 CUDA tensor of the same bytes."""
+    sp = _stream_ptr(stream)
+    args = (int(device), ctypes.byref(camera.raw), int(width), int(height))
+    if hasattr(px, "is_cuda") and px.is_cuda:
+        if not (hasattr(py, "is_cuda") and py.is_cuda) or px.device != py.device:
+            raise TypeError("px and py must both be CUDA tensors on one device")
+        for t in (px, py):
+            if t.dtype not in (torch.int32, torch.uint32):
+                raise TypeError("px/py must be int32 or uint32 tensors")
+        px, py = px.contiguous().reshape(-1), py.contiguous().reshape(-1)
+        if px.shape[0] != py.shape[0]:
+            raise ValueError("px and py lengths differ")
+        n = px.shape[0]
+        rays = torch.empty((n, 8), dtype=torch.float32, device=px.device)
+        if n:
+            check(lib().vr_camera_rays(*args, c_void_p(px.data_ptr()), c_void_p(py.data_ptr()), n, 1,
+                                       c_void_p(rays.data_ptr()), 1, sp), "vr_camera_rays")
+        return rays
+    px = np.ascontiguousarray(px, dtype=np.uint32).reshape(-1)
+    py = np.ascontiguousarray(py, dtype=np.uint32).reshape(-1)
+    if px.shape[0] != py.shape[0]:
+        raise ValueError("px and py lengths differ")
+    n = px.shape[0]
+    rays = np.zeros(n, dtype=RAY_DTYPE)
+    if n:
+        check(lib().vr_camera_rays(*args, px.ctypes.data_as(c_void_p), py.ctypes.data_as(c_void_p), n, 0,
+                                   rays.ctypes.data_as(c_void_p), 0, sp), "vr_camera_rays")
+    return rays
 
 
 def band_buffer_words(width: int, height: int, band_rows: int, nranks: int) -> int:
