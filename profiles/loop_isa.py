@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Print the innermost loops that hold a global_load_dwordx2 in one kernel of
 an ISA listing (hipcc -S / --save-temps), with VALU/SALU instruction counts.
-  python profiles/loop_isa.py build/isa_vr_march-hip-amdgcn-amd-amdhsa-gfx950.s march_kernelILi0ELi1ELb0E [--print]"""
+  python profiles/loop_isa.py build/vr_march-hip-amdgcn-amd-amdhsa-gfx950.s march_kernelILi0ELi1ELb0E [--print]"""
 import re
 import sys
 

@@ -8,7 +8,7 @@ counters that moved (vr_diag_fetch, read and zeroed after each frame).
     VR_LIBRARY=voxelraymarcher_amd/libvr_cover.so python -m tests.cover_run
 
 GUARDS names every counter index of the build: what it counts and the cases expected to move
-it.  32 and up stand beside the rarely-taken blocks that keep the walks exact (vr_march.hip);
+it.  32 and up stand beside the rarely-taken blocks that keep the walks exact (vr_walk.h);
 0-25 are the hot-loop counters of profiles/wave_counts.py, listed so that no index is without
 an owner."""
 from __future__ import annotations
@@ -86,7 +86,7 @@ GUARDS = {
     58: ("shadow walks, sign pattern 7 (+ + +)", ("E1-mixed",) + _TINY_LIGHT),
 }
 # index: where the argument that no finite input reaches it is written (and tried: LOW, ALIAS)
-UNREACHABLE = {37: "vr_march.hip walk_longest_vcs, at the site; DESIGN.md section 4; "
+UNREACHABLE = {37: "vr_walk.h walk_longest_vcs, at the site; DESIGN.md section 4; "
                    "tests/test_edge_cases.py::test_no_jump_starts_in_a_negative_cell"}
 
 

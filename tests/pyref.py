@@ -26,7 +26,7 @@ iteration that leaves the loop's state unchanged repeats forever) render as
 0.  Cluster-skip crawls -- an axis pinned on its skip plane that EPSILON * d
 cannot move, so every iteration in the cluster moves the ray by RN(EPSILON *
 d) -- are run in closed form with exact rational arithmetic (crawl_run), a
-formulation independent of the GPU's float fast-forward (vr_march.hip
+formulation independent of the GPU's float fast-forward (vr_crawl.h
 crawl_steps) and of the C oracle, which walks them iteration by iteration.
 """
 from __future__ import annotations

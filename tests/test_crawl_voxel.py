@@ -1,5 +1,5 @@
 """CPU check of the crawl-voxel recovery behind the crawl pass's resume
-(vr_march.hip crawl_voxel): a crawl iteration stepped o <- RN(o + c),
+(vr_crawl.h crawl_voxel): a crawl iteration stepped o <- RN(o + c),
 c = RN(EPSILON * d); the deferral record keeps only the stepped position, and
 the voxel q = trunc(old o) is recovered from it as the truncation shared by
 every float within 4 steps of RN(o - c) that steps to o, or declared ambiguous

@@ -259,7 +259,7 @@ def test_counting_build_is_apart_from_the_library():
 
 
 def test_no_jump_starts_in_a_negative_cell(monkeypatch):
-    """The evidence beside the argument (vr_march.hip at the site) that the
+    """The evidence beside the argument (vr_walk.h at the site) that the
     longest-axis walk's negative-cell cluster plane is never needed: over the alias fixture (whose
     walks do probe outside their region: the oracle counts them), a view made to leave a sparse
     block through its three low faces (edge_cases.low_face_case) and the tiny-direction cases

@@ -75,7 +75,7 @@ def test_guards_are_reached():
     per store x algorithm through the counting build (the same sources with -DVR_DIAG), compares
     each frame with the oracle and reports the counters that moved.  Every counter of GUARDS moved
     in at least one of the cases named for it, or stands in UNREACHABLE with its argument (beside
-    the site in vr_march.hip and in DESIGN.md section 4)."""
+    the site in vr_walk.h and in DESIGN.md section 4)."""
     assert os.path.exists(COVER_LIB), "libvr_cover.so is not built (make -C voxelraymarcher_amd/csrc)"
     env = dict(os.environ, VR_LIBRARY=COVER_LIB)
     p = subprocess.run([sys.executable, "-m", "tests.cover_run"], cwd=ROOT, env=env, capture_output=True, text=True,

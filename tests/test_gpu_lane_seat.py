@@ -1,4 +1,4 @@
-"""GPU test of the lane order's seats (vr_march.hip perm_kernel, lane_pixel): a repeated view
+"""GPU test of the lane order's seats (vr_order.hip perm_kernel, vr_march.hip lane_pixel): a repeated view
 learns, per pixel block, which 64 pixels each wave slot renders (the cost-rank deal) and in
 which lane of the slot each pixel sits (VR_LANE_SEAT: cost order or ascending Morton order of
 the pixel's column and row in the block).  The order is read back through

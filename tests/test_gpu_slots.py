@@ -59,7 +59,7 @@ def test_launches_in_flight_on_three_streams(c5_scene, kernel, algo):
 
 
 def test_crawl_skip_safety_net(c5_scene):
-    """The crawl-pass skip's safety net (vr_launch_plan.h CrawlSkip, vr_march.hip deferral_report).
+    """The crawl-pass skip's safety net (vr_launch_plan.h CrawlSkip, vr_walk.h deferral_report).
     Every slot first learns a view that defers nothing (C5's top rows: each slot's last crawl
     pass reports 0).  Then the next launch is forced to skip its crawl pass on C5's crawl rows,
     as a wrong skip would: its deferred pixels stay 0 (the frame differs).  Its tile pass

@@ -1,7 +1,7 @@
 // vr_crawl.h -- the closed-form fast-forward of cluster-skip crawls (crawl_steps,
 // crawl_run) and the voxel recovery behind the crawl pass's resume (crawl_voxel).
 // Pure float arithmetic, no memory but the region's cluster bits: compiled for the
-// device by vr_march.hip, which uses it, and for both sides by tools/crawl_check.hip,
+// device with vr_walk.h, which uses it, and for both sides by tools/crawl_check.hip,
 // which holds it against a plain single-step loop (tests/test_crawl_check.py).
 // Two things differ between the sides: the reciprocal of crawl_floor (crawl_rcp) and
 // the bit casts (crawl_bits / crawl_float: the device's __float_as_uint /

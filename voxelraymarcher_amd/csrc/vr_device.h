@@ -1,5 +1,6 @@
 // vr_device.h -- device-side building blocks of the ray-march kernels
-// (vr_march.hip: the tile pass, one lane per pixel, and the crawl pass):
+// (vr_walk.h: the Walker; vr_march.hip: the tile pass, one lane per pixel, and the crawl
+// pass; vr_query.hip: pick and trace):
 // math with the reference's operation order, CUDA-semantics conversions,
 // the storage lookups and the lighting.  FP policy: SURVEY.md 8(c).
 #pragma once

@@ -1,5 +1,5 @@
 // vr_internal.h -- layouts shared by the host builder (vr_scene.cpp) and the
-// HIP kernels (vr_march.hip).  See DESIGN.md "Data layout in HBM".
+// HIP kernels (vr_march.hip, vr_order.hip, vr_query.hip, vr_util.hip; the walker: vr_walk.h).  See DESIGN.md "Data layout in HBM".
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -159,11 +159,11 @@ struct KView {
 static_assert(sizeof(KView) - offsetof(KView, out) == 104,
               "a KView field was added after `out`: review whether it belongs to the view identity");
 
-// Rays that start a cluster-skip crawl (see vr_march.hip crawl_steps) in the
+// Rays that start a cluster-skip crawl (see vr_crawl.h crawl_steps) in the
 // tile pass, and pixels that exceed kTileBudget, are deferred to a second pass
 // over a per-launch list.
 // A slot is [count, done, overflow, 0] and kDeferCap records of kDeferRecWords
-// words: the crawling walk's state at the crawl (vr_march.hip, grid_original_rt),
+// words: the crawling walk's state at the crawl (vr_walk.h, grid_original_rt),
 // from which the crawl pass resumes it, or just the pixel (flag 4: walk it from
 // its start).  Record words:
 //   0 pixel (row << 16 | x)   1 flags (1 shadow walk, 2 longest-axis shadow, 4 walk from the start)
@@ -185,7 +185,7 @@ hipError_t launch_march(int store, int algo, bool count, const KScene& s, const 
                         hipStream_t stream, uint32_t crawl_wgs, bool in_flight, bool crawl = true);
 // Crawl-pass grid for a launch that expects about `records` deferred pixels.
 uint32_t crawl_grid(uint32_t records, uint32_t rpw);
-// vr_pick's kernel: the primary hit behind each of n pixels (px[i], py[i]) of the view's frame
+// vr_pick's kernel (vr_query.hip, as the two below): the primary hit behind each of n pixels (px[i], py[i]) of the view's frame
 // as 64-byte vr_hit records (hits: 16-byte aligned device memory), one lane per query with the
 // exact walker.  The view is make_view's with one band over the frame; nothing below `out` is read.
 constexpr uint32_t kPickMiss = 0, kPickVoxel = 1, kPickNever = 2, kPickOutside = 3;   // = VR_HIT_*
@@ -208,6 +208,7 @@ hipError_t launch_camera_rays(const KView& v, const uint32_t* px, const uint32_t
 // already freed and null).
 hipError_t trace_order(const KScene& s, const KView& v, const void* rays, uint32_t n, hipStream_t stream,
                        void** scratch, const uint32_t** idx);
+// (vr_util.hip, to launch_assemble_tiles)
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);
 // ht_filter of a cuckoo scene from its tables (one workgroup per region).
@@ -227,6 +228,7 @@ hipError_t launch_assemble_tiles(const void* parts, void* frame, uint32_t elem_b
 // The tile pass's grid for a view (columns, rows of workgroups) and its waves per workgroup.
 void march_grid(const KView& v, uint32_t& columns, uint32_t& rows);
 constexpr uint32_t kWavesPerTileGroup = 2;
+// (vr_order.hip, to launch_perm)
 // Heaviest-first work order of a grid of `columns` x `n / columns` workgroups from the
 // costs a launch wrote (KView::cost): one workgroup, a counting sort by cost.
 hipError_t launch_order(const uint32_t* cost, uint32_t n, uint32_t columns, uint32_t* order, hipStream_t stream);
@@ -235,7 +237,7 @@ hipError_t launch_order(const uint32_t* cost, uint32_t n, uint32_t columns, uint
 // also the waves' walk lengths under the new lane order (KView::cost's layout).
 size_t perm_bytes(uint32_t gx, uint32_t gy);   // the lane order of a gx x gy grid
 // How the build lays a lane order out: the block's sides in pixels, the bytes of one perm
-// entry and the seat rule (vr_march.hip VR_LANE_SEAT) -- for vr_debug_lane_order's readers.
+// entry and the seat rule (vr_lane_order.h VR_LANE_SEAT) -- for vr_debug_lane_order's readers.
 struct LaneShape {
     uint32_t block_x, block_y, entry_bytes, seat;
 };

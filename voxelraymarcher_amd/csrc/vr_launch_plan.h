@@ -75,7 +75,7 @@ struct WorkOrder : Learned {
     void learned(uint32_t x, uint32_t y, uint64_t k, bool ok) { Learned::learned(x, y, k, ok); relaned = false; }
     void forget() { valid = relaned = false; }
 };
-// Per slot: the lane order (vr_march.hip lane_pixel): per lane block (16x32 pixels) its pixels heaviest first.
+// Per slot: the lane order (vr_march.hip lane_pixel, vr_order.hip perm_kernel): per lane block (16x32 pixels) its pixels heaviest first.
 struct LaneOrder : Learned {
     uint8_t* perm = nullptr;       // vr::perm_bytes(gx, gy)
     size_t bcap = 0;
@@ -92,7 +92,7 @@ inline uint32_t next_launch_id(uint32_t& serial) { return ++serial ? serial : ++
 // leaves raise the count the next crawl pass of the slot reports, which ends the skipping.
 // (C2 lone launch: the 4-us empty crawl pass and a kernel boundary.)
 //   The safety net: every tile pass that defers a pixel writes {launch id, 1}
-// into the slot's report word (vr_march.hip deferral_report), skipped launches included.
+// into the slot's report word (vr_walk.h deferral_report), skipped launches included.
 // While the slot skips, nothing else writes that word (its last crawl pass left
 // {id, 0}), so a nonzero count there means a skipped launch deferred: the skipping ends,
 // and the slot's next launch runs the crawl pass, which drops the stale records (they

@@ -1,5 +1,5 @@
 // vr_trace.hip -- the coherent execution order of vr_trace (include/vr.h): a 64-bit key per ray
-// and a stable radix sort of (key, ray index); trace_kernel (vr_march.hip) then walks ray
+// and a stable radix sort of (key, ray index); trace_kernel (vr_query.hip) then walks ray
 // idx[i] in lane i, so the lanes of a wave start near each other and head the same way.  The
 // order decides only which lane walks which ray: no record depends on it.
 //

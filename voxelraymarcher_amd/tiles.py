@@ -58,7 +58,7 @@ def tile_words(width: int, height: int, band_rows: int, tile_cols: int, nranks: 
 def tile_source_index(width: int, height: int, band_rows: int, tile_cols: int, nranks: int,
                       stride: int = 0) -> torch.Tensor:
     """For every frame pixel (row-major), its index in the nranks tile buffers laid back to back:
-    the inverse of the 2-D deal (vr_internal.h KView, vr_march.hip assemble_tiles_kernel)."""
+    the inverse of the 2-D deal (vr_internal.h KView, vr_util.hip assemble_tiles_kernel)."""
     s = deal_stride(nranks, stride)
     words = tile_words(width, height, band_rows, tile_cols, nranks)
     lw = tile_local_width(width, tile_cols, nranks)
