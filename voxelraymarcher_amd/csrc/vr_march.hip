@@ -104,8 +104,10 @@ __device__ __forceinline__ uint32_t* tile_prim() {
 
 // applyLighting at the primary hit (Renderer.cuh:249-258; regionWorldPosition :413)
 // times !shadow (:315,737,821): the pixel's colour.
-template <int STORE, bool COUNT, bool CRAWL>
+// (ALGO: the original algorithm's kernels take the shadow walk's sign arms, Walker::shadow)
+template <int ALGO, int STORE, bool COUNT, bool CRAWL>
 __device__ __forceinline__ uint32_t light_and_shadow(Walker<STORE, COUNT, CRAWL>& w, const KView& v, const Hit& h) {
+    constexpr bool kArms = ALGO == ALGO_ORIGINAL;
     bool sh = false;
     const f3 rwp = add(ld3(v.translation), mk((float)(h.region.x * kBlock), (float)(h.region.y * kBlock),
                                               (float)(h.region.z * kBlock)));
@@ -118,7 +120,8 @@ __device__ __forceinline__ uint32_t light_and_shadow(Walker<STORE, COUNT, CRAWL>
             w.ctx = 2u;
             sh = w.template shadow<true>(h.so, h.region);
         } else {
-            sh = eq ? w.template shadow<false, true>(h.so, h.region) : w.template shadow<false>(h.so, h.region);
+            sh = eq ? w.template shadow<false, true, kArms>(h.so, h.region)
+                    : w.template shadow<false, false, kArms>(h.so, h.region);
         }
     }
     return lit * (uint32_t)!sh;
@@ -173,7 +176,7 @@ __device__ __forceinline__ uint32_t shade(const KScene& s, const KView& v, uint3
         Hit h;
         const bool hit = w.template primary<ALGO>(ro, rd, h);
         if (!CRAWL && v.pcost) tile_prim()[threadIdx.x] = w.iters;   // (the lane order's primary walk length)
-        if (hit) col = light_and_shadow(w, v, h);
+        if (hit) col = light_and_shadow<ALGO>(w, v, h);
         if (iters) *iters = w.iters;              // the walk's length (the work order's cost)
         bytes = w.bytes + 4u;                     // + the pixel write
         if (ff) *ff = uint2{w.ff, w.nl};
@@ -212,7 +215,7 @@ __device__ __forceinline__ uint32_t shade_resume(const KScene& s, const KView& v
         f3 ro, rd;
         pixel_ray<true>(v, x, l, ro, rd);
         Hit h;
-        if (w.template primary_regions<ALGO>(o, rd, cr, h, r)) col = light_and_shadow(w, v, h);
+        if (w.template primary_regions<ALGO>(o, rd, cr, h, r)) col = light_and_shadow<ALGO>(w, v, h);
     } else {                                      // the shadow walk crawled
         const bool eq = v.L[0] == v.L[1] && v.L[1] == v.L[2];
         bool sh;

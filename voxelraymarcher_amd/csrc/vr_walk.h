@@ -74,6 +74,25 @@ __device__ __forceinline__ int32_t plane_c8(int32_t c8) {
 #define VR_LONG_TAIL_EQ 0
 #endif
 
+// VR_SHADOW_ARMS (the tile pass's original shadow walk, both stores): the light's sign pattern
+// is uniform, so it is dispatched on once per shadow ray with scalar branches -- the ray's whole
+// sequence of region walks runs inside the arm of its pattern (Walker::arms, shadow_regions)
+// -- instead of once per region round inside grid_original_rt, and the arm's set-up is
+// specialised like its loop.  C2 per frame in flight 0.0949 -> 0.0933 ms, SQ_INSTS_VALU per
+// launch 7.46e7 -> 7.27e7, identical frames (profiles/setup/).  0: the dispatch per round, as
+// the primary walk and the longest-axis walks' tails keep it -- the same arms around the
+// primary walk, where the pattern differs per lane, measured slower.
+#ifndef VR_SHADOW_ARMS
+#define VR_SHADOW_ARMS 1
+#endif
+// What an arm's region walks share, made once per ray: nlim = 2^-90 where the direction's
+// three reciprocals are in div_fast's domain and no component is a guarded zero (walk_ok),
+// else +inf; okw = every lane that entered the arm has walk_ok (uniform).
+struct ArmRay {
+    float nlim;
+    bool okw;
+};
+
 // The iteration count of a tile-pass walk that wrote a crawl record (see the deferral
 // in grid_original_rt): the pixel is the crawl pass's already.
 constexpr uint32_t kDeferredIters = 0xFFFFFFFFu;
@@ -168,13 +187,26 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
     // (nullptr: made here).
     // generic: one loop for every sign pattern (the longest-axis walks' rare
     // original-DDA tails: less code and register demand in that kernel)
+    // AX, AY, AZ, aw (the tile pass's original shadow walk, see arms): the caller runs inside
+    // the arm of the ray's sign pattern -- +1 / -1 per axis, or 2, 2, 2 for all positive with the
+    // reciprocals in div_fast's domain; rc and aw are then the ray's.  No dispatch here:
+    // the signs, the +-1, +-EPSILON and cluster-offset constants and the planes of the
+    // initial step fold at compile time.  0, 0, 0: the signs are read from d in here.
+    template <int AX = 0, int AY = 0, int AZ = 0>
     __device__ __forceinline__ bool grid_original_rt(f3& o, f3 d, uint32_t reg, i3 cr, Hit& h, const bool SHADOW,
                                                      const bool EQ, const uint32_t* rs = nullptr,
-                                                     const Rcp* rc = nullptr, const bool generic = false) {
+                                                     const Rcp* rc = nullptr, const bool generic = false,
+                                                     const ArmRay* aw = nullptr) {
+        constexpr bool kArm = AX != 0;
+        static_assert(!kArm || !CRAWL, "sign arms are the tile pass's");
+        // the set-up's plane signs (plane_v: 0 = per lane)
+        constexpr int BX = AX > 0 ? 1 : AX, BY = AY > 0 ? 1 : AY, BZ = AZ > 0 ? 1 : AZ;
         const bool resume = CRAWL && rs != nullptr;
         VR_DIAG_COUNT(SHADOW ? 9 : 8);                 // grid_original calls
-        const bool px = d.x > 0.0f, py = d.y > 0.0f, pz = d.z > 0.0f;
-        const bool zx = SHADOW && d.x == 0.0f, zy = SHADOW && d.y == 0.0f, zz = SHADOW && d.z == 0.0f;
+        const bool px = kArm ? AX > 0 : d.x > 0.0f, py = kArm ? AY > 0 : d.y > 0.0f, pz = kArm ? AZ > 0 : d.z > 0.0f;
+        // (a positive component is not zero)
+        const bool zx = SHADOW && !(kArm && AX > 0) && d.x == 0.0f, zy = SHADOW && !(kArm && AY > 0) && d.y == 0.0f,
+                   zz = SHADOW && !(kArm && AZ > 0) && d.z == 0.0f;
         float tX, tY, tZ;
         if (resume) {                             // o is the stepped position of the crawl
             tX = __uint_as_float(rs[11]); tY = __uint_as_float(rs[12]); tZ = __uint_as_float(rs[13]);
@@ -187,10 +219,13 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
             const Rcp r0x = use_rc ? rc[0] : rcp_setup(d.x), r0y = use_rc ? rc[1] : rcp_setup(d.y),
                       r0z = use_rc ? rc[2] : rcp_setup(d.z);
             const float sx = px ? 1.0f : -1.0f, sy = py ? 1.0f : -1.0f, sz = pz ? 1.0f : -1.0f;
-            const float ax = next_plane_fma(o.x, sx, sx * kEps) - o.x, ay = next_plane_fma(o.y, sy, sy * kEps) - o.y,
-                        az = next_plane_fma(o.z, sz, sz * kEps) - o.z;
-            const bool fast = r0x.ok && r0y.ok && r0z.ok && !zx && !zy && !zz &&
-                              fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= 0x1p-90f;
+            const float ax = plane_v<BX>(o.x, sx, sx * kEps) - o.x, ay = plane_v<BY>(o.y, sy, sy * kEps) - o.y,
+                        az = plane_v<BZ>(o.z, sz, sz * kEps) - o.z;
+            // (an arm: aw->nlim is 2^-90 where the three reciprocals are in the domain and no
+            // component is a guarded zero, else +inf)
+            const bool fast = kArm ? fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= aw->nlim
+                                   : r0x.ok && r0y.ok && r0z.ok && !zx && !zy && !zz &&
+                                         fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az))) >= 0x1p-90f;
             tX = div_fast(ax, r0x); tY = div_fast(ay, r0y); tZ = div_fast(az, r0z);
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) != 0, 0)) {
                 VR_DIAG_COUNT(32);                     // initial step: a lane outside div_fast's domain
@@ -271,10 +306,12 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                 const int32_t cx8 = px ? 8 : 0, cy8 = py ? 8 : 0, cz8 = pz ? 8 : 0;
                 // A guarded zero direction component (shadow ray) keeps the lane on the
                 // slow branch, which applies the guard: the fast path needs no selects.
-                const bool walk_ok = rx.ok && ry.ok && rz.ok && !zx && !zy && !zz;
                 // one compare per iteration: min |n| >= lim (lim = +inf sends the lane
                 // to the slow branch every iteration; |n| < 73 inside a region)
-                const float nlim = walk_ok ? 0x1p-90f : kInf;
+                // (an arm: both made once per ray)
+                const float nlim0 = kArm ? aw->nlim : 0.0f;
+                const bool walk_ok = kArm ? nlim0 < kInf : rx.ok && ry.ok && rz.ok && !zx && !zy && !zz;
+                const float nlim = kArm ? nlim0 : (walk_ok ? 0x1p-90f : kInf);
                 if (resume_now) {
                     // the deferred crawl: its iteration left an absent cluster (blk) at
                     // voxel q with o stepped; the post-loop test below re-finds the crawl
@@ -304,7 +341,8 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                         // plane (ceilf(o) + EPSILON, floorf(o) - EPSILON) lies >= ~EPSILON/2 from
                         // o -- so the domain check runs only in wave-iterations where some lane
                         // skips (a scalar branch; -2 VALU per iteration without a skip).
-                        const bool okw = __builtin_amdgcn_ballot_w64(!walk_ok) == 0;
+                        // (an arm: the ray's, uniform)
+                        const bool okw = kArm ? aw->okw : __builtin_amdgcn_ballot_w64(!walk_ok) == 0;
                         VR_DIAG_COUNT((SHADOW ? 4 : 0) + (SX == 0 ? 1 : 0));   // walk entries
                         for (;;) {
                             VR_DIAG_COUNT((SHADOW ? 6 : 2) + (SX == 0 ? 1 : 0));   // loop iterations
@@ -421,7 +459,11 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                     const uint32_t sg = (px ? 1u : 0u) | (py ? 2u : 0u) | (pz ? 4u : 0u);
                     using N = Sgn<-1>;
                     using P = Sgn<1>;
-                    if (CRAWL || generic) {
+                    if constexpr (kArm) {
+                        // the caller's arm: this region's walk of its lanes, no dispatch
+                        VR_DIAG_PAT(SHADOW, (AX > 0 ? 1 : 0) | (AY > 0 ? 2 : 0) | (AZ > 0 ? 4 : 0));
+                        walk(Sgn<AX>{}, Sgn<AY>{}, Sgn<AZ>{});
+                    } else if (CRAWL || generic) {
                         walk(Sgn<0>{}, Sgn<0>{}, Sgn<0>{});
                     } else {
                         // One pass of the loop specialised for each sign pattern present in
@@ -552,22 +594,27 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
             o = add(o, f3{0.0f, 0.0f, 0.0f});      // -0 -> +0 (in_region_bits_nz below)
             if (!this->in_region_bits_nz(o)) return false;
             if (aborted || this->iters >= kBudget) { aborted = true; return false; }
-            const Rcp rx = rcp_setup(EQ ? fabsf(d.x) : d.x), ry = rcp_setup(d.y), rz = rcp_setup(d.z);
+            // (an arm: the ray's reciprocals; rcp_setup(|d|) = |rcp_setup(d)|, see the VCS walk)
+            const bool arm_rc = kArm && rc;
+            const Rcp rx = arm_rc ? (EQ ? Rcp{fabsf(d.x), fabsf(rc[0].r), rc[0].ok} : rc[0]) : rcp_setup(EQ ? fabsf(d.x) : d.x),
+                      ry = arm_rc ? rc[1] : rcp_setup(d.y), rz = arm_rc ? rc[2] : rcp_setup(d.z);
             const float gx = px ? 1.0f : -1.0f, gy = py ? 1.0f : -1.0f, gz = pz ? 1.0f : -1.0f;
             const float ex = gx * kEps, ey = gy * kEps, ez = gz * kEps;
-            const bool walk_ok = rx.ok && ry.ok && rz.ok && !zx && !zy && !zz;
-            const float nlim = walk_ok ? 0x1p-90f : kInf;
+            // (an arm: walk_ok, nlim and okw are the ray's, see the VCS walk)
+            const float nlim0 = kArm ? aw->nlim : 0.0f;
+            const bool walk_ok = kArm ? nlim0 < kInf : rx.ok && ry.ok && rz.ok && !zx && !zy && !zz;
+            const float nlim = kArm ? nlim0 : (walk_ok ? 0x1p-90f : kInf);
             // no cluster skips here: with every lane's direction in div_fast's domain no
             // numerator (a voxel plane's, >= ~EPSILON/2 from o) leaves it -- no check at all
-            const bool okw = __builtin_amdgcn_ballot_w64(!walk_ok) == 0;
+            const bool okw = kArm ? aw->okw : __builtin_amdgcn_ballot_w64(!walk_ok) == 0;
             // the region's filter words (64-bit: a cuckoo scene has no region bound, vr_internal.h)
             const uint32_t* freg = s.ht_filter + (size_t)reg * kHashFilterWords;
             uint32_t fw = 0, bit = 0;
             uint32_t ic = this->iters + (0x42800000u - kBudget);   // biased count (see the VCS walk)
             // rayMarchVoxelGrid's voxel step (Renderer.cuh:318-331) from o: its t values, min
             auto voxel_step = [&](float& sX, float& sY, float& sZ) -> float {
-                const float ax = next_plane_fma(o.x, gx, ex) - o.x, ay = next_plane_fma(o.y, gy, ey) - o.y,
-                            az = next_plane_fma(o.z, gz, ez) - o.z;
+                const float ax = plane_v<BX>(o.x, gx, ex) - o.x, ay = plane_v<BY>(o.y, gy, ey) - o.y,
+                            az = plane_v<BZ>(o.z, gz, ez) - o.z;
                 if (EQ) {                                 // see grid_original
                     const float am = fminf(fabsf(ax), fminf(fabsf(ay), fabsf(az)));
                     float sMin = div_fast(am, rx);
@@ -1231,6 +1278,39 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
         f3 o = sub(so, mk((float)(cr.x * kBlock), (float)(cr.y * kBlock), (float)(cr.z * kBlock)));
         return primary_regions<ALGO>(o, d, cr, h, nullptr, rc);
     }
+    // The tile pass's original shadow walk dispatches on the light's sign pattern once per ray.
+    static constexpr bool kShadowArms = VR_SHADOW_ARMS && !CRAWL;
+    // Run f in the arm of the uniform sign pattern sg (bit 0: d.x > 0, bit 1: y, bit 2: z):
+    // f(Sgn<+-1>..., ArmRay) -- for pattern 7, Sgn<2> three times when walk_ok holds.  sg and
+    // walk_ok are the light's, the same in every lane: the branches are scalar (s_cmp,
+    // s_cbranch_scc), no lane mask is made.  EQ (equal components): only patterns 0 and 7 exist.
+    template <bool EQ, class F>
+    __device__ __forceinline__ bool arms(uint32_t sg, bool walk_ok, F&& f) {
+        const uint32_t p = __builtin_amdgcn_readfirstlane(sg);
+        ArmRay aw;
+        aw.nlim = walk_ok ? 0x1p-90f : kInf;
+        aw.okw = walk_ok;
+        using N = Sgn<-1>;
+        using P = Sgn<1>;
+        using Q = Sgn<2>;
+        if (p == 7u) {
+            if (aw.okw) return f(Q{}, Q{}, Q{}, aw);
+            VR_DIAG_COUNT(42);         // a lane's walk_ok failed: P,P,P with checks
+            return f(P{}, P{}, P{}, aw);
+        }
+        if (p == 0u) return f(N{}, N{}, N{}, aw);
+        if constexpr (!EQ) {
+            switch (p) {
+            case 1: return f(P{}, N{}, N{}, aw);
+            case 2: return f(N{}, P{}, N{}, aw);
+            case 3: return f(P{}, P{}, N{}, aw);
+            case 4: return f(N{}, N{}, P{}, aw);
+            case 5: return f(P{}, N{}, P{}, aw);
+            default: return f(N{}, P{}, P{}, aw);
+            }
+        }
+        return false;
+    }
     // The region walk of rayMarchVoxelScene(LongestAxis) (:376-433); rs (crawl
     // pass): first finish the region walk a deferral record left at its crawl.
     template <int ALGO>
@@ -1274,12 +1354,31 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
 
     // isInShadowOriginalRayMarch (Renderer.cuh:174-235) /
     // isInShadowRayMarchVoxelSceneLongestAxis (:633-694).
-    template <bool LONGEST, bool EQ = false>
+    // ARMS: dispatch on the light's sign pattern here, once per ray (see arms).  The original
+    // algorithm's tile pass asks for it; the longest-axis kernel, whose rare original-DDA hits
+    // also come here, keeps the dispatch per round (less code in a kernel that spills: with the
+    // arms C3 ran 0.1791 -> 0.1840 ms per frame in flight, profiles/setup/).
+    template <bool LONGEST, bool EQ = false, bool ARMS = false>
     __device__ __forceinline__ bool shadow(f3 o, i3 cr, const uint32_t* rs = nullptr) {
         f3 d = ld3(v.L);
         // the light's reciprocals, made on the host (uniform: SGPRs, no VGPRs)
         const bool lf = v.L_fast != 0u;
         const Rcp rc[3] = {Rcp{d.x, v.Lr[0], lf}, Rcp{d.y, v.Lr[1], lf}, Rcp{d.z, v.Lr[2], lf}};
+        if constexpr (kShadowArms && ARMS && !LONGEST) {
+            // the light's sign pattern and walk_ok are uniform: scalar branches to its arm
+            const uint32_t sg = (d.x > 0.0f ? 1u : 0u) | (d.y > 0.0f ? 2u : 0u) | (d.z > 0.0f ? 4u : 0u);
+            const bool walk_ok = lf && d.x != 0.0f && d.y != 0.0f && d.z != 0.0f;
+            return arms<EQ>(sg, walk_ok, [&](auto ax, auto ay, auto az, const ArmRay& aw) __attribute__((always_inline)) {
+                return shadow_regions<LONGEST, EQ, decltype(ax)::value, decltype(ay)::value, decltype(az)::value>(
+                    o, d, cr, nullptr, rc, &aw);
+            });
+        } else {
+            return shadow_regions<LONGEST, EQ>(o, d, cr, rs, rc);
+        }
+    }
+    template <bool LONGEST, bool EQ, int AX = 0, int AY = 0, int AZ = 0>
+    __device__ __forceinline__ bool shadow_regions(f3 o, f3 d, i3 cr, const uint32_t* rs, const Rcp* rc,
+                                                   const ArmRay* aw = nullptr) {
         Hit dummy;
         if (CRAWL && rs != nullptr) {            // resume a deferred crawl (as primary_regions)
             const bool hit = grid_original_rt(o, d, this->region_at_nocount(cr), cr, dummy, true, EQ, rs);
@@ -1300,9 +1399,13 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                 if (!this->template skip_null<!LONGEST>(cr, o, d, reg)) return false;
                 if (kExact && this->cycle_step(cyc1, cr, o)) { aborted = true; return false; }   // (as above)
             }
-            bool hit = LONGEST ? (STORE == STORE_VCS ? grid_longest_vcs<true>(o, d, reg, cr, dummy)
-                                                     : grid_longest<true>(o, d, reg, cr, dummy))
-                               : grid_original<true, EQ>(o, d, reg, cr, dummy, nullptr, rc);
+            bool hit;
+            if constexpr (AX != 0)
+                hit = this->template grid_original_rt<AX, AY, AZ>(o, d, reg, cr, dummy, true, EQ, nullptr, rc, false, aw);
+            else
+                hit = LONGEST ? (STORE == STORE_VCS ? grid_longest_vcs<true>(o, d, reg, cr, dummy)
+                                                    : grid_longest<true>(o, d, reg, cr, dummy))
+                              : grid_original<true, EQ>(o, d, reg, cr, dummy, nullptr, rc);
             if (aborted) return false;
             if (hit) return true;
             advance_region(cr, o);
