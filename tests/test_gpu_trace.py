@@ -231,6 +231,44 @@ def test_batch_prefix_and_sentinel(batch, n, order):
     got = dh.cpu().numpy()
     assert got[:n].tobytes() == b["full"][:n].tobytes()
     assert (got[n] == 0x5A5A5A5A).all()
+    # the mixed forms: device rays to host records, host rays to device records
+    hits = np.full(n + 1, 0xAB, dtype=np.uint8).repeat(64).view(vr.HIT_DTYPE)
+    raw_trace(b["scene"], ORIGINAL, b["info"], b["drays"], n, hits, True, False, order)
+    assert hits[:n].tobytes() == b["full"][:n].tobytes()
+    assert hits[n].tobytes() == bytes([0xAB]) * 64
+    dh = torch.full((n + 1, 16), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    raw_trace(b["scene"], ORIGINAL, b["info"], b["rays"], n, dh, False, True, order)
+    got = dh.cpu().numpy()
+    assert got[:n].tobytes() == b["full"][:n].tobytes()
+    assert (got[n] == 0x5A5A5A5A).all()
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_camera_rays_every_staging_mode(n):
+    """vr_camera_rays with its pixels and its rays each on the host or on the device: all four
+    forms give the bytes of the host/host call for n pixels of the 32 x 24 golden frame, and
+    record n of an n + 1 record buffer is never written."""
+    W, H = 32, 24
+    cam = vr.Camera.reference(W, H)
+    px, py = (a[:n].copy() for a in frame_pixels(W, H))
+    dpx, dpy = (torch.from_numpy(a.view(np.int32)).cuda() for a in (px, py))
+    want = vr.camera_rays(cam, W, H, px, py)
+    assert want.tobytes() == trace_ref.camera_rays(cam, W, H, px, py).tobytes()
+    ptr = lambda a: ctypes.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)   # noqa: E731
+    for in_dev in (False, True):
+        for out_dev in (False, True):
+            if out_dev:
+                rays = torch.full((n + 1, 8), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+            else:
+                rays = np.full(n + 1, 0xAB, dtype=np.uint8).repeat(32).view(vr.RAY_DTYPE)
+            qx, qy = (dpx, dpy) if in_dev else (px, py)
+            vr._capi.check(vr.lib().vr_camera_rays(0, ctypes.byref(cam.raw), W, H, ptr(qx), ptr(qy), n, int(in_dev),
+                                                   ptr(rays), int(out_dev),
+                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                           "vr_camera_rays")
+            got = rays.cpu().numpy() if out_dev else rays
+            assert got[:n].tobytes() == want.tobytes(), (in_dev, out_dev)
+            assert got[n].tobytes() == (bytes([0x5A]) if out_dev else bytes([0xAB])) * 32, (in_dev, out_dev)
 
 
 # ---------------------------------------------------------------- 6. orders agree

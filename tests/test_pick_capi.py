@@ -62,6 +62,9 @@ def test_invalid_arguments_name_vr_pick():
         invalid(_call(lib, fake, cam, tr, W, H, p, p, 1, h), "size")
     invalid(_call(lib, fake, cam, tr, 8, 8, p, p, 1 << 31, h), "many")
     invalid(_call(lib, fake, cam, tr, 8, 8, p, p, 1, h, algo=7), "algorithm")
+    # device hits must be 16-byte aligned: checked on the pointer alone, beside the other checks
+    off8 = ctypes.c_void_p(hits.ctypes.data + 8)
+    invalid(lib.vr_pick(fake, 1, cam, tr, 1, 8, 8, p, p, 1, 0, off8, 1, None), "aligned")
     assert not hits.tobytes().strip(b"\0")                                   # nothing was written
     assert _call(lib, fake, cam, tr, 8, 8, None, None, 0, None) == 0          # n == 0: nothing to do
     assert _call(lib, fake, cam, tr, 65536, 65536, p, p, 0, h) == 0

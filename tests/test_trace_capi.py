@@ -88,8 +88,8 @@ def test_camera_rays_invalid_arguments_name_vr_camera_rays():
     rays = np.zeros(4, dtype=vr.RAY_DTYPE)
     p, r = q.ctypes.data_as(ctypes.c_void_p), rays.ctypes.data_as(ctypes.c_void_p)
 
-    def call(device=0, c=cam, W=8, H=8, px=p, py=p, n=1, rr=r):
-        return lib.vr_camera_rays(device, c, W, H, px, py, n, 0, rr, 0, None)
+    def call(device=0, c=cam, W=8, H=8, px=p, py=p, n=1, rr=r, out_dev=0):
+        return lib.vr_camera_rays(device, c, W, H, px, py, n, 0, rr, out_dev, None)
 
     def invalid(rc, word):
         assert rc == -1 and "vr_camera_rays" in _last_error() and word in _last_error(), _last_error()
@@ -102,6 +102,9 @@ def test_camera_rays_invalid_arguments_name_vr_camera_rays():
     invalid(call(n=1 << 31), "many")
     for device in (-1, 64, 1000):
         invalid(call(device=device), "device")
+    # device rays must be 16-byte aligned (checked on the pointer alone)
+    for off in (4, 8):
+        invalid(call(rr=ctypes.c_void_p(rays.ctypes.data + off), out_dev=1), "aligned")
     assert not rays.tobytes().strip(b"\0")                    # nothing was written
     assert call(px=None, py=None, rr=None, n=0) == 0
     assert call(W=65536, H=65536, n=0) == 0

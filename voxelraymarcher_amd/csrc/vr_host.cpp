@@ -1,6 +1,7 @@
 // vr_host.cpp -- the thread's error string and the camera and lighting maths of the C ABI
 // (include/vr.h).  The rest of libvr.so's host side: vr_scene.cpp (scene build and upload),
-// vr_scene_io.cpp (synthetic grids, .vox/.vxb files), vr_launch.cpp (the render launch).
+// vr_scene_io.cpp (synthetic grids, .vox/.vxb files), vr_launch.cpp (the render launch),
+// vr_query_api.cpp (vr_pick, vr_trace, vr_camera_rays).
 //
 // Replaces Camera::Camera (renderer/camera/Camera.cuh:11-23).
 #include <cmath>

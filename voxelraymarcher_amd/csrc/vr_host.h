@@ -1,5 +1,6 @@
 // vr_host.h -- what the host translation units of libvr.so share (vr_host.cpp, vr_scene.cpp,
-// vr_scene_io.cpp, vr_launch.cpp).  Private: nothing declared here is exported.
+// vr_scene_io.cpp, vr_launch.cpp, vr_query_api.cpp).  Private: nothing declared here is exported.
+// (vr_staging.h, beside it: the staging buffers of the entry points that take host or device arrays.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,18 @@ namespace vr {
 inline int fail(int code, const std::string& msg) { return set_error(code, msg); }
 inline int hip_fail(hipError_t e, const char* what) {
     return fail(VR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// Nothing of `who` (an entry point, as its messages name it) can be captured into a HIP graph:
+// it waits for the stream, allocates, or keeps host-side state that a replay would not redo.
+// Called before anything is enqueued or allocated.
+inline int refuse_capture(hipStream_t st, const char* who) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(VR_E_INVALID, std::string(who) + " cannot be captured into a HIP graph (stream is capturing)");
+    return VR_OK;
 }
 
 struct DeviceGuard {
@@ -75,6 +88,12 @@ namespace vr {
 KScene kscene(const vr_scene* s);
 int build_scene(int device, vr_store store, const int32_t* xyz, const uint32_t* rgb, size_t n, bool on_device,
                 vr_build mode, void* stream, vr_scene** out);
+
+// vr_launch.cpp: the camera and frame size of a view (v.W, v.H, v.LW; nothing else is written),
+// and the whole view of a render (zeroed first; the launch's rows and tile deal are the caller's)
+void view_camera(KView& v, const vr_camera* cam, uint32_t width, uint32_t height);
+int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, const float translation[3],
+              uint32_t scale, uint32_t width, uint32_t height, KView& v);
 
 // vr_scene_io.cpp: a scene file's voxels (.vxb or .vox CSV, read and parsed once)
 struct VoxParse {

@@ -1,7 +1,7 @@
 // vr_launch.cpp -- the render launch: the per-device slot ring, the learned orders and the
-// crawl-pass skip kept per slot (their decisions: vr_launch_plan.h), and the render entry
-// points of include/vr.h; vr_pick, which shares the view but none of the launch state, and
-// vr_trace / vr_camera_rays, which share neither.
+// crawl-pass skip kept per slot (their decisions: vr_launch_plan.h), the render entry points of
+// include/vr.h with the view they render (make_view; vr_query_api.cpp's pick shares it and
+// nothing else), the band and tile helpers and the vr_debug_* functions.
 //
 // Replaces runRaymarchingKernel (main/Main.cu:105-163).
 #include <algorithm>
@@ -22,21 +22,26 @@
 #include "vr_launch_plan.h"
 #pragma GCC visibility pop
 
-namespace {
+namespace vr {
 
-using vr::DeviceGuard;
-using vr::fail;
-using vr::hip_fail;
+void view_camera(KView& v, const vr_camera* cam, uint32_t width, uint32_t height) {
+    for (int i = 0; i < 3; ++i) {
+        v.llc[i] = cam->lower_left[i]; v.hor[i] = cam->horizontal[i]; v.ver[i] = cam->vertical[i];
+        v.org[i] = cam->origin[i];
+    }
+    v.W = width;
+    v.H = height;
+    v.LW = width;
+}
 
 int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, const float translation[3],
-              uint32_t scale, uint32_t width, uint32_t height, vr::KView& v) {
+              uint32_t scale, uint32_t width, uint32_t height, KView& v) {
     if (!s) return fail(VR_E_INVALID, "scene is NULL");
     if (!cam || !lit) return fail(VR_E_INVALID, "camera/lighting NULL");
     if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "bad image size");
     memset(&v, 0, sizeof v);
+    view_camera(v, cam, width, height);
     for (int i = 0; i < 3; ++i) {
-        v.llc[i] = cam->lower_left[i]; v.hor[i] = cam->horizontal[i]; v.ver[i] = cam->vertical[i];
-        v.org[i] = cam->origin[i];
         v.L[i] = lit->light_dir[i]; v.LC[i] = lit->light_color[i]; v.LP[i] = lit->light_pos[i];
         v.translation[i] = translation ? translation[i] : 0.0f;
     }
@@ -67,11 +72,17 @@ int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, c
     v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
     v.use_point_light = lit->use_point_light ? 1 : 0;
     v.use_shadows = lit->use_shadows ? 1 : 0;
-    v.W = width;
-    v.H = height;
-    v.LW = width;
     return VR_OK;
 }
+
+}  // namespace vr
+
+namespace {
+
+using vr::DeviceGuard;
+using vr::fail;
+using vr::hip_fail;
+using vr::make_view;
 
 // ---------------------------------------------------------------- environment knobs
 // Each is read once per process (a function-local static): none is on the per-launch path.
@@ -348,18 +359,6 @@ hipError_t bind_lane_order(vr::LaneOrder& L, uint32_t gx, uint32_t gy, uint64_t 
     return hipMallocAsync((void**)&v.pcost, sizeof(uint32_t) * (size_t)v.LW * v.local_rows, st);
 }
 
-// A launch is not capturable into a graph: the slot ring's event wait/record and the
-// work order's host-side bookkeeping would be baked into it and not replay (no test
-// captures one), so capture is refused before anything is enqueued.
-int refuse_capture(hipStream_t st) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(st, &cap);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(VR_E_INVALID, "vr_render* cannot be captured into a HIP graph (stream is capturing)");
-    return VR_OK;
-}
-
 // VR_ORDER_CHECK (debugging): read a new work order back and report whether it is a
 // permutation of the grid.  (getenv per order build: off the steady-state path.)
 void order_check(const vr::WorkOrder& W, uint32_t slot, uint32_t gx, uint32_t gy) {
@@ -415,7 +414,10 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
     if (v.local_rows == 0 || v.LW == 0) return VR_OK;
     DeviceGuard dg(s->device);
     const hipStream_t st = (hipStream_t)stream;
-    int rc = refuse_capture(st);
+    // A launch is not capturable into a graph: the slot ring's event wait/record and the
+    // work order's host-side bookkeeping would be baked into it and not replay (no test
+    // captures one), so capture is refused before anything is enqueued.
+    int rc = vr::refuse_capture(st, "vr_render*");
     if (rc) return rc;
     // the deferral list of the crawl pass (cluster-skip crawls, walks over the tile budget)
     SlotLease lease;
@@ -572,205 +574,6 @@ int vr_render_ex(const vr_scene* s, vr_algo algo, const vr_camera* cam, const vr
     v.defer_cap = o.defer_cap;
     if (o.schedule > VR_SCHEDULE_HEAVIEST_FIRST) return fail(VR_E_INVALID, "unknown schedule");
     return launch(s, algo, o.kernel, o.schedule, o.occupancy, v, stream);
-}
-
-// The hit behind each pixel (vr.h).  Not a render launch: no slot lease, no view key, no
-// D.follow / D.alone bookkeeping -- nothing the render path keeps per device is touched.
-int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam, const float translation[3], uint32_t scale,
-            uint32_t width, uint32_t height, const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
-            vr_hit* hits, int outputs_on_device, void* stream) {
-    static_assert(sizeof(vr_hit) == 64 && offsetof(vr_hit, voxel) == 8 && offsetof(vr_hit, normal) == 20 &&
-                      offsetof(vr_hit, region) == 32 && offsetof(vr_hit, point) == 44 && offsetof(vr_hit, reserved) == 56,
-                  "vr_hit: the record pick_kernel writes");
-    static_assert(vr::kPickMiss == VR_HIT_MISS && vr::kPickVoxel == VR_HIT_VOXEL && vr::kPickNever == VR_HIT_NEVER &&
-                      vr::kPickOutside == VR_HIT_OUTSIDE, "VR_HIT_*");
-    if (!s) return fail(VR_E_INVALID, "vr_pick: scene is NULL");
-    if (!cam || !translation) return fail(VR_E_INVALID, "vr_pick: camera/translation NULL");
-    if (n && (!px || !py || !hits)) return fail(VR_E_INVALID, "vr_pick: px/py/hits NULL");
-    if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "vr_pick: bad image size");
-    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_pick: too many queries");
-    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_pick: unknown algorithm");
-    if (n == 0) return VR_OK;
-    // the view of a whole-frame render: one band, rank 0 of 1 (the lights are never read)
-    vr_lighting lit;
-    vr_lighting_default(&lit);
-    vr::KView v;
-    int rc = make_view(s, cam, &lit, translation, scale, width, height, v);
-    if (rc) return rc;
-    v.row_limit = height;
-    v.band_rows = height;
-    v.band_minv = height == 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / height);
-    v.nranks = 1;
-    v.local_rows = height;
-    DeviceGuard dg(s->device);
-    const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &cap);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(VR_E_INVALID, "vr_pick cannot be captured into a HIP graph (stream is capturing)");
-    const uint32_t *dpx = px, *dpy = py;
-    void *tq = nullptr, *th = nullptr;      // staging owned by this call: {px, py}, hits
-    auto release = [&]() {
-        if (tq) (void)hipFree(tq);
-        if (th) (void)hipFree(th);
-    };
-    if (!inputs_on_device) {
-        e = hipMalloc(&tq, 2 * n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(tq, px, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((uint32_t*)tq + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { release(); return hip_fail(e, "vr_pick: query upload"); }
-        dpx = (const uint32_t*)tq;
-        dpy = dpx + n;
-    }
-    void* dh = hits;
-    if (!outputs_on_device) {
-        e = hipMalloc(&th, n * sizeof(vr_hit));
-        if (e != hipSuccess) { release(); return hip_fail(e, "vr_pick: hit buffer"); }
-        dh = th;
-    } else if (((uintptr_t)hits & 15u) != 0u) {
-        release();
-        return fail(VR_E_INVALID, "vr_pick: device hits must be 16-byte aligned");
-    }
-    e = vr::launch_pick((int)s->store, (int)algo, vr::kscene(s), v, dpx, dpy, (uint32_t)n, dh, st);
-    if (e == hipSuccess && !outputs_on_device)
-        e = hipMemcpyAsync(hits, th, n * sizeof(vr_hit), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    release();
-    if (e != hipSuccess) return hip_fail(e, "vr_pick");
-    return VR_OK;
-}
-
-// The closest hit of arbitrary rays (vr.h).  As vr_pick: not a render launch, nothing the render
-// path keeps per device is touched.  Every argument check comes before any device work.
-int vr_trace(const vr_scene* s, vr_algo algo, const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
-             int inputs_on_device, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream) {
-    static_assert(sizeof(vr_ray) == 32 && offsetof(vr_ray, reserved0) == 12 && offsetof(vr_ray, direction) == 16 &&
-                      offsetof(vr_ray, reserved1) == 28, "vr_ray: the record trace_kernel loads");
-    if (!s) return fail(VR_E_INVALID, "vr_trace: scene is NULL");
-    if (!translation) return fail(VR_E_INVALID, "vr_trace: translation NULL");
-    if (n && (!rays || !hits)) return fail(VR_E_INVALID, "vr_trace: rays/hits NULL");
-    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_trace: too many rays");
-    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_trace: unknown algorithm");
-    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
-        return fail(VR_E_INVALID, "vr_trace: unknown order");
-    if (n == 0) return VR_OK;
-    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
-        return fail(VR_E_INVALID, "vr_trace: device rays must be 16-byte aligned");
-    if (outputs_on_device && ((uintptr_t)hits & 15u) != 0u)
-        return fail(VR_E_INVALID, "vr_trace: device hits must be 16-byte aligned");
-    // the walk reads the view's translation and scale only (no camera, no light, no frame)
-    vr::KView v;
-    memset(&v, 0, sizeof v);
-    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
-    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
-    // AUTO is GIVEN at every n: COHERENT won at no measured size (vr.h, profiles/trace/README.md)
-    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
-    DeviceGuard dg(s->device);
-    const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &cap);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(VR_E_INVALID, "vr_trace cannot be captured into a HIP graph (stream is capturing)");
-    void *tr = nullptr, *th = nullptr, *to = nullptr;     // owned by this call: rays, hits, the order's scratch
-    auto release = [&]() {
-        if (tr) (void)hipFree(tr);
-        if (th) (void)hipFree(th);
-        if (to) (void)hipFree(to);
-    };
-    const void* dr = rays;
-    if (!inputs_on_device) {
-        e = hipMalloc(&tr, n * sizeof(vr_ray));
-        if (e == hipSuccess) e = hipMemcpyAsync(tr, rays, n * sizeof(vr_ray), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_trace: ray upload"); }
-        dr = tr;
-    }
-    void* dh = hits;
-    if (!outputs_on_device) {
-        e = hipMalloc(&th, n * sizeof(vr_hit));
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_trace: hit buffer"); }
-        dh = th;
-    }
-    const uint32_t* idx = nullptr;
-    if (coherent) e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &to, &idx);
-    if (e == hipSuccess) e = vr::launch_trace((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, dh, st);
-    if (e == hipSuccess && !outputs_on_device)
-        e = hipMemcpyAsync(hits, th, n * sizeof(vr_hit), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    release();
-    if (e != hipSuccess) return hip_fail(e, "vr_trace");
-    return VR_OK;
-}
-
-// The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.
-int vr_camera_rays(int device, const vr_camera* cam, uint32_t width, uint32_t height, const uint32_t* px,
-                   const uint32_t* py, size_t n, int inputs_on_device, vr_ray* rays, int outputs_on_device, void* stream) {
-    if (!cam) return fail(VR_E_INVALID, "vr_camera_rays: camera NULL");
-    if (n && (!px || !py || !rays)) return fail(VR_E_INVALID, "vr_camera_rays: px/py/rays NULL");
-    if (width == 0 || height == 0 || width > 65536 || height > 65536)
-        return fail(VR_E_INVALID, "vr_camera_rays: bad image size");
-    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_camera_rays: too many pixels");
-    if (device < 0 || device > 63) return fail(VR_E_INVALID, "vr_camera_rays: bad device");
-    if (n == 0) return VR_OK;
-    if (outputs_on_device && ((uintptr_t)rays & 15u) != 0u)
-        return fail(VR_E_INVALID, "vr_camera_rays: device rays must be 16-byte aligned");
-    // the view of a whole-frame render: one band, rank 0 of 1 (as vr_pick's); only the camera is read
-    vr::KView v;
-    memset(&v, 0, sizeof v);
-    for (int i = 0; i < 3; ++i) {
-        v.llc[i] = cam->lower_left[i]; v.hor[i] = cam->horizontal[i]; v.ver[i] = cam->vertical[i];
-        v.org[i] = cam->origin[i];
-    }
-    v.W = width;
-    v.H = height;
-    v.LW = width;
-    v.row_limit = height;
-    v.band_rows = height;
-    v.band_minv = height == 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / height);
-    v.nranks = 1;
-    v.local_rows = height;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(VR_E_INVALID, "vr_camera_rays: no such device");
-    DeviceGuard dg(device);
-    const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &cap);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(VR_E_INVALID, "vr_camera_rays cannot be captured into a HIP graph (stream is capturing)");
-    const uint32_t *dpx = px, *dpy = py;
-    void *tq = nullptr, *tr = nullptr;      // staging owned by this call: {px, py}, rays
-    auto release = [&]() {
-        if (tq) (void)hipFree(tq);
-        if (tr) (void)hipFree(tr);
-    };
-    if (!inputs_on_device) {
-        e = hipMalloc(&tq, 2 * n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(tq, px, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((uint32_t*)tq + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_camera_rays: pixel upload"); }
-        dpx = (const uint32_t*)tq;
-        dpy = dpx + n;
-    }
-    void* dr = rays;
-    if (!outputs_on_device) {
-        e = hipMalloc(&tr, n * sizeof(vr_ray));
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); release(); return hip_fail(e, "vr_camera_rays: ray buffer"); }
-        dr = tr;
-    }
-    e = vr::launch_camera_rays(v, dpx, dpy, (uint32_t)n, dr, st);
-    if (e == hipSuccess && !outputs_on_device)
-        e = hipMemcpyAsync(rays, tr, n * sizeof(vr_ray), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    release();
-    if (e != hipSuccess) return hip_fail(e, "vr_camera_rays");
-    return VR_OK;
 }
 
 int vr_render_opts_init(vr_render_opts* opts) {

@@ -7,9 +7,6 @@
 namespace vr {
 namespace {
 
-// The 64-byte hit record (include/vr.h vr_hit) of a primary walk that has ended: w the
-// walker (its aborted flag: a walk that never finishes; its PickCell), h its Hit, hit what
-// primary() returned.  The hit voxel goes through the store's key x << 20 | y << 10 | z and back.
 // Pick (vr_pick): the primary hit of pixel (px[i], py[i]) as a 64-byte record, one lane per
 // query, with the exact walker (the crawl pass's: every walk runs to its end, crawls are
 // fast-forwarded, a walk that never finishes is detected) and nothing else -- no lighting,

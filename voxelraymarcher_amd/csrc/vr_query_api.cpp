@@ -1,0 +1,168 @@
+// vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace and
+// vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip).  None is a render launch: no slot
+// lease, no view key, nothing the render path keeps per device (vr_launch.cpp) is touched.  Each
+// takes its arrays on the host or on the device (vr_staging.h), and in each every argument
+// check comes before any device work.
+#include <cstddef>
+#include <cstring>
+
+#include "vr_host.h"
+#include "vr_staging.h"
+
+namespace {
+
+using vr::DeviceGuard;
+using vr::fail;
+using vr::hip_fail;
+using vr::Staging;
+
+// The rows of a whole-frame render: one band, rank 0 of 1 (in a zeroed view).
+void whole_frame(vr::KView& v, uint32_t height) {
+    v.row_limit = height;
+    v.band_rows = height;
+    v.band_minv = height == 1u ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / height);
+    v.nranks = 1;
+    v.local_rows = height;
+}
+
+// The n pixels (px[i], py[i]) on the device: the caller's own arrays, or host arrays staged in
+// one buffer, py behind px.  Null after an error (sg.err).
+const uint32_t* pixels_on_device(Staging& sg, const uint32_t* px, const uint32_t* py, size_t n, const uint32_t*& dpy) {
+    uint32_t* q = (uint32_t*)sg.make(2 * n * sizeof(uint32_t));
+    sg.put(q, px, n * sizeof(uint32_t));
+    sg.put(q + n, py, n * sizeof(uint32_t));
+    dpy = q + n;
+    return sg.err == hipSuccess ? q : nullptr;
+}
+
+// The end of every query: the records' way back to a host array, the wait for the stream, and
+// the first error of kernel launch `e`, copy and wait under the entry point's name.
+int finish(Staging& sg, hipError_t e, void* host, const void* dev, size_t bytes, const char* who) {
+    if (e == hipSuccess && host != dev) {
+        sg.fetch(host, dev, bytes);
+        e = sg.err;
+    }
+    const hipError_t es = sg.sync();
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, who);
+    return VR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The hit behind each pixel (vr.h).
+int vr_pick(const vr_scene* s, vr_algo algo, const vr_camera* cam, const float translation[3], uint32_t scale,
+            uint32_t width, uint32_t height, const uint32_t* px, const uint32_t* py, size_t n, int inputs_on_device,
+            vr_hit* hits, int outputs_on_device, void* stream) {
+    static_assert(sizeof(vr_hit) == 64 && offsetof(vr_hit, voxel) == 8 && offsetof(vr_hit, normal) == 20 &&
+                      offsetof(vr_hit, region) == 32 && offsetof(vr_hit, point) == 44 && offsetof(vr_hit, reserved) == 56,
+                  "vr_hit: the record pick_kernel writes");
+    static_assert(vr::kPickMiss == VR_HIT_MISS && vr::kPickVoxel == VR_HIT_VOXEL && vr::kPickNever == VR_HIT_NEVER &&
+                      vr::kPickOutside == VR_HIT_OUTSIDE, "VR_HIT_*");
+    if (!s) return fail(VR_E_INVALID, "vr_pick: scene is NULL");
+    if (!cam || !translation) return fail(VR_E_INVALID, "vr_pick: camera/translation NULL");
+    if (n && (!px || !py || !hits)) return fail(VR_E_INVALID, "vr_pick: px/py/hits NULL");
+    if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "vr_pick: bad image size");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_pick: too many queries");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_pick: unknown algorithm");
+    if (n == 0) return VR_OK;
+    if (outputs_on_device && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_pick: device hits must be 16-byte aligned");
+    // the view of a whole-frame render (the lights are never read)
+    vr_lighting lit;
+    vr_lighting_default(&lit);
+    vr::KView v;
+    int rc = vr::make_view(s, cam, &lit, translation, scale, width, height, v);
+    if (rc) return rc;
+    whole_frame(v, height);
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if ((rc = vr::refuse_capture(st, "vr_pick"))) return rc;
+    Staging sg(st);
+    const uint32_t *dpx = px, *dpy = py;
+    if (!inputs_on_device) dpx = pixels_on_device(sg, px, py, n, dpy);
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_pick: query upload");
+    void* dh = outputs_on_device ? hits : sg.make(n * sizeof(vr_hit));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_pick: hit buffer");
+    const hipError_t e = vr::launch_pick((int)s->store, (int)algo, vr::kscene(s), v, dpx, dpy, (uint32_t)n, dh, st);
+    return finish(sg, e, hits, dh, n * sizeof(vr_hit), "vr_pick");
+}
+
+// The closest hit of arbitrary rays (vr.h).
+int vr_trace(const vr_scene* s, vr_algo algo, const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
+             int inputs_on_device, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream) {
+    static_assert(sizeof(vr_ray) == 32 && offsetof(vr_ray, reserved0) == 12 && offsetof(vr_ray, direction) == 16 &&
+                      offsetof(vr_ray, reserved1) == 28, "vr_ray: the record trace_kernel loads");
+    if (!s) return fail(VR_E_INVALID, "vr_trace: scene is NULL");
+    if (!translation) return fail(VR_E_INVALID, "vr_trace: translation NULL");
+    if (n && (!rays || !hits)) return fail(VR_E_INVALID, "vr_trace: rays/hits NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_trace: too many rays");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS) return fail(VR_E_INVALID, "vr_trace: unknown algorithm");
+    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
+        return fail(VR_E_INVALID, "vr_trace: unknown order");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_trace: device rays must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_trace: device hits must be 16-byte aligned");
+    // the walk reads the view's translation and scale only (no camera, no light, no frame)
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
+    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
+    // AUTO is GIVEN at every n: COHERENT won at no measured size (vr.h, profiles/trace/README.md)
+    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_trace")) return rc;
+    Staging sg(st);
+    const void* dr = inputs_on_device ? rays : sg.upload(rays, n * sizeof(vr_ray));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_trace: ray upload");
+    void* dh = outputs_on_device ? hits : sg.make(n * sizeof(vr_hit));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_trace: hit buffer");
+    hipError_t e = hipSuccess;
+    const uint32_t* idx = nullptr;
+    if (coherent) {
+        void* scratch = nullptr;
+        e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &scratch, &idx);
+        sg.adopt(scratch);
+    }
+    if (e == hipSuccess) e = vr::launch_trace((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, dh, st);
+    return finish(sg, e, hits, dh, n * sizeof(vr_hit), "vr_trace");
+}
+
+// The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.
+int vr_camera_rays(int device, const vr_camera* cam, uint32_t width, uint32_t height, const uint32_t* px,
+                   const uint32_t* py, size_t n, int inputs_on_device, vr_ray* rays, int outputs_on_device, void* stream) {
+    if (!cam) return fail(VR_E_INVALID, "vr_camera_rays: camera NULL");
+    if (n && (!px || !py || !rays)) return fail(VR_E_INVALID, "vr_camera_rays: px/py/rays NULL");
+    if (width == 0 || height == 0 || width > 65536 || height > 65536)
+        return fail(VR_E_INVALID, "vr_camera_rays: bad image size");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_camera_rays: too many pixels");
+    if (device < 0 || device > 63) return fail(VR_E_INVALID, "vr_camera_rays: bad device");
+    if (n == 0) return VR_OK;
+    if (outputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_camera_rays: device rays must be 16-byte aligned");
+    // the view of a whole-frame render, as vr_pick's; only the camera is read
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    vr::view_camera(v, cam, width, height);
+    whole_frame(v, height);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(VR_E_INVALID, "vr_camera_rays: no such device");
+    DeviceGuard dg(device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_camera_rays")) return rc;
+    Staging sg(st);
+    const uint32_t *dpx = px, *dpy = py;
+    if (!inputs_on_device) dpx = pixels_on_device(sg, px, py, n, dpy);
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_camera_rays: pixel upload");
+    void* dr = outputs_on_device ? rays : sg.make(n * sizeof(vr_ray));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_camera_rays: ray buffer");
+    const hipError_t e = vr::launch_camera_rays(v, dpx, dpy, (uint32_t)n, dr, st);
+    return finish(sg, e, rays, dr, n * sizeof(vr_ray), "vr_camera_rays");
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 
 #include "vr_build.h"
 #include "vr_host.h"
+#include "vr_staging.h"
 
 namespace {
 
@@ -23,6 +24,7 @@ using vr::DevBuf;
 using vr::DeviceGuard;
 using vr::fail;
 using vr::hip_fail;
+using vr::Staging;
 
 // static_cast<int32_t>(float) with the CUDA semantics used on the device.
 inline int32_t f2i(float f) {
@@ -279,30 +281,20 @@ int build_scene_host(int device, vr_store store, const int32_t* xyz, const uint3
     return VR_OK;
 }
 
-// Device build (vr_build.hip) from host or device voxel arrays.
-int build_scene_device(int device, vr_store store, const int32_t* xyz, const uint32_t* rgb, size_t n, bool on_device,
-                       hipStream_t stream, vr_scene** out) {
-    DeviceGuard dg(device);
-    const int32_t* dxyz = xyz;
-    const uint32_t* drgb = rgb;
-    void *tx = nullptr, *tc = nullptr;
-    auto release = [&]() {
-        if (tx) (void)hipFree(tx);
-        if (tc) (void)hipFree(tc);
-    };
-    if (!on_device && n) {
-        hipError_t e = hipMalloc(&tx, 3 * n * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&tc, n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(tx, xyz, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tc, rgb, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { release(); return hip_fail(e, "voxel upload"); }
-        dxyz = (const int32_t*)tx;
-        drgb = (const uint32_t*)tc;
-    }
-    vr::GpuScene g;
-    std::string err;
-    const int rc = vr::build_scene_gpu((int)store, dxyz, drgb, n, stream, g, err);
-    release();
+// The n voxels (xyz, rgb) on the device: the caller's own arrays, or host arrays staged in two
+// buffers (both made, then both filled).  Null after an error (sg.err).
+const int32_t* voxels_on_device(Staging& sg, const int32_t* xyz, const uint32_t* rgb, size_t n, const uint32_t*& drgb) {
+    void* tx = sg.make(3 * n * sizeof(int32_t));
+    void* tc = sg.make(n * sizeof(uint32_t));
+    sg.put(tx, xyz, 3 * n * sizeof(int32_t));
+    sg.put(tc, rgb, n * sizeof(uint32_t));
+    drgb = (const uint32_t*)tc;
+    return sg.err == hipSuccess ? (const int32_t*)tx : nullptr;
+}
+
+// A scene that owns what a device builder made (vr_build.h): whatever `g` holds, after a failed
+// build too, is freed with the scene.
+ScenePtr adopt_scene(int device, vr_store store, const vr::GpuScene& g) {
     ScenePtr s = new_scene(device, store);
     s->D = g.D; s->min_coord = g.min_coord;
     s->n_regions = g.n_regions; s->n_voxels = g.n_voxels;
@@ -311,7 +303,27 @@ int build_scene_device(int device, vr_store store, const int32_t* xyz, const uin
     s->vcs_vals = DevBuf{g.vcs_vals, g.vcs_vals_bytes};
     s->ht_meta = DevBuf{g.ht_meta, g.ht_meta_bytes};
     s->ht_slots = DevBuf{g.ht_slots, g.ht_slots_bytes};
-    if (rc) return fail(rc == -1 ? VR_E_INVALID : rc == -5 ? VR_E_BUILD : VR_E_HIP, "scene build: " + err);
+    return s;
+}
+
+// What the device builders return (vr_build.h), as the C ABI's code.
+int builder_code(int rc) { return rc == -1 ? VR_E_INVALID : rc == -5 ? VR_E_BUILD : VR_E_HIP; }
+
+// Device build (vr_build.hip) from host or device voxel arrays.
+int build_scene_device(int device, vr_store store, const int32_t* xyz, const uint32_t* rgb, size_t n, bool on_device,
+                       hipStream_t stream, vr_scene** out) {
+    DeviceGuard dg(device);
+    Staging sg(stream);
+    const int32_t* dxyz = xyz;
+    const uint32_t* drgb = rgb;
+    if (!on_device && n) dxyz = voxels_on_device(sg, xyz, rgb, n, drgb);
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "voxel upload");
+    vr::GpuScene g;
+    std::string err;
+    const int rc = vr::build_scene_gpu((int)store, dxyz, drgb, n, stream, g, err);
+    if (rc == 0) sg.drained();   // (a build that succeeds returns after the stream has drained)
+    ScenePtr s = adopt_scene(device, store, g);
+    if (rc) return fail(builder_code(rc), "scene build: " + err);
     *out = s.release();
     return VR_OK;
 }
@@ -464,41 +476,22 @@ int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n
     if (n >= 0xFFFFFFFFull) return fail(VR_E_INVALID, "vr_scene_edit: too many edits");
     DeviceGuard dg(s->device);
     const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &cap);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(VR_E_INVALID, "vr_scene_edit cannot be captured into a HIP graph (stream is capturing)");
-    const int32_t* dxyz = xyz;
-    const uint32_t* drgb = rgb;
-    void *tx = nullptr, *tc = nullptr;
-    auto release = [&]() {
-        if (tx) (void)hipFree(tx);
-        if (tc) (void)hipFree(tc);
-    };
-    if (!inputs_on_device) {
-        e = hipMalloc(&tx, 3 * n * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&tc, n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(tx, xyz, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(tc, rgb, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { release(); return hip_fail(e, "edit upload"); }
-        dxyz = (const int32_t*)tx;
-        drgb = (const uint32_t*)tc;
-    }
-    vr::GpuScene g;
-    std::string err;
-    const int rc = vr::edit_scene_gpu(gpu_image(s), dxyz, drgb, n, st, g, err);
-    release();
+    if (const int rc = vr::refuse_capture(st, "vr_scene_edit")) return rc;
     // the new image as a scene of its own: freed whole if anything fails, swapped in otherwise
-    ScenePtr t = new_scene(s->device, s->store);
-    t->D = g.D; t->min_coord = g.min_coord;
-    t->n_regions = g.n_regions; t->n_voxels = g.n_voxels;
-    t->region_slot = DevBuf{g.region_slot, g.region_slot_bytes};
-    t->vcs_mask = DevBuf{g.vcs_mask, g.vcs_mask_bytes};
-    t->vcs_vals = DevBuf{g.vcs_vals, g.vcs_vals_bytes};
-    t->ht_meta = DevBuf{g.ht_meta, g.ht_meta_bytes};
-    t->ht_slots = DevBuf{g.ht_slots, g.ht_slots_bytes};
-    if (rc) return fail(rc == -1 ? VR_E_INVALID : rc == -5 ? VR_E_BUILD : VR_E_HIP, "scene edit: " + err);
+    ScenePtr t;
+    {
+        Staging sg(st);
+        const int32_t* dxyz = xyz;
+        const uint32_t* drgb = rgb;
+        if (!inputs_on_device) dxyz = voxels_on_device(sg, xyz, rgb, n, drgb);
+        if (sg.err != hipSuccess) return hip_fail(sg.err, "edit upload");
+        vr::GpuScene g;
+        std::string err;
+        const int rc = vr::edit_scene_gpu(gpu_image(s), dxyz, drgb, n, st, g, err);
+        if (rc == 0) sg.drained();   // (as a build: an edit that succeeds has drained the stream)
+        t = adopt_scene(s->device, s->store, g);
+        if (rc) return fail(builder_code(rc), "scene edit: " + err);
+    }
     if (const int rd = add_derived_bits(t.get(), st)) return rd;
     // the stream has drained (add_derived_bits): renders queued on it before the edit are done
     std::swap(s->n_regions, t->n_regions);
@@ -523,30 +516,19 @@ int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capac
     if (m == 0) return VR_OK;
     DeviceGuard dg(s->device);
     const hipStream_t st = (hipStream_t)stream;
-    int32_t* dxyz = xyz;
-    uint32_t* drgb = rgb;
-    void *tx = nullptr, *tc = nullptr;
-    auto release = [&]() {
-        if (tx) (void)hipFree(tx);
-        if (tc) (void)hipFree(tc);
-    };
-    hipError_t e = hipSuccess;
-    if (!outputs_on_device) {
-        e = hipMalloc(&tx, 3 * m * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&tc, m * sizeof(uint32_t));
-        if (e != hipSuccess) { release(); return hip_fail(e, "voxel export buffers"); }
-        dxyz = (int32_t*)tx;
-        drgb = (uint32_t*)tc;
-    }
+    // (No vr::refuse_capture here, unlike every other entry point that stages: vr_scene_voxels
+    // never refused a capturing stream, and that is left as it was.)
+    Staging sg(st);
+    int32_t* dxyz = outputs_on_device ? xyz : (int32_t*)sg.make(3 * m * sizeof(int32_t));
+    uint32_t* drgb = outputs_on_device ? rgb : (uint32_t*)sg.make(m * sizeof(uint32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "voxel export buffers");
     std::string err;
     const int rc = vr::export_scene_gpu(gpu_image(s), dxyz, drgb, st, err);
-    if (rc == 0 && !outputs_on_device) {
-        e = hipMemcpyAsync(xyz, tx, 3 * m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(rgb, tc, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    release();
-    if (rc) return fail(rc == -1 ? VR_E_INVALID : VR_E_HIP, "scene export: " + err);
+    if (rc) return fail(builder_code(rc), "scene export: " + err);
+    if (outputs_on_device) return VR_OK;
+    sg.fetch(xyz, dxyz, 3 * m * sizeof(int32_t));
+    sg.fetch(rgb, drgb, m * sizeof(uint32_t));
+    const hipError_t e = sg.err == hipSuccess ? sg.sync() : sg.err;
     if (e != hipSuccess) return hip_fail(e, "voxel download");
     return VR_OK;
 }

@@ -470,6 +470,39 @@ HIT_DTYPE = np.dtype([("status", "<u4"), ("color", "<u4"), ("voxel", "<i4", (3,)
 assert HIT_DTYPE.itemsize == ctypes.sizeof(_capi.VrHit) == 64
 
 
+def _ptr(a) -> c_void_p:
+    """The address of a CUDA tensor's or a numpy array's first element."""
+    return c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def _pixel_lists(px, py):
+    """px/py of pick and camera_rays as flat arrays: (px, py, n, on_device) -- contiguous CUDA
+    tensors when px is one, uint32 numpy arrays otherwise."""
+    on_device = hasattr(px, "is_cuda") and px.is_cuda
+    if on_device:
+        if not (hasattr(py, "is_cuda") and py.is_cuda) or px.device != py.device:
+            raise TypeError("px and py must both be CUDA tensors on one device")
+        for t in (px, py):
+            if t.dtype not in (torch.int32, torch.uint32):
+                raise TypeError("px/py must be int32 or uint32 tensors")
+        px, py = px.contiguous().reshape(-1), py.contiguous().reshape(-1)
+    else:
+        px = np.ascontiguousarray(px, dtype=np.uint32).reshape(-1)
+        py = np.ascontiguousarray(py, dtype=np.uint32).reshape(-1)
+    if px.shape[0] != py.shape[0]:
+        raise ValueError("px and py lengths differ")
+    return px, py, px.shape[0], on_device
+
+
+def _records(n: int, dtype: np.dtype, like):
+    """The result of a query of n records of `dtype`: beside a CUDA tensor `like`, an (n, words)
+    tensor on its device (float32 for rays, int32 for hits); otherwise a zeroed numpy array."""
+    if hasattr(like, "is_cuda") and like.is_cuda:
+        return torch.empty((n, dtype.itemsize // 4), dtype=torch.float32 if dtype == RAY_DTYPE else torch.int32,
+                           device=like.device)
+    return np.zeros(n, dtype=dtype)
+
+
 def pick(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, width: int,
          height: int, px, py, stream=None):
     """vr_pick: the voxel, face and hit point behind pixels (px[i], py[i]) of the width x height
@@ -479,33 +512,12 @@ def pick(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info:
     device give an (n, 16) int32 CUDA tensor of the same bytes.  `voxel` is what
     DeviceScene.edit takes; `normal` is the reference's shading normal.  Runs on `stream`
     (default: the current stream) and returns when the records are written."""
-    sp = _stream_ptr(stream)
     args = (scene.handle, int(algorithm), ctypes.byref(camera.raw), f3(info.translation), int(info.scale), int(width),
             int(height))
-    if hasattr(px, "is_cuda") and px.is_cuda:
-        if not (hasattr(py, "is_cuda") and py.is_cuda) or px.device != py.device:
-            raise TypeError("px and py must both be CUDA tensors on one device")
-        for t in (px, py):
-            if t.dtype not in (torch.int32, torch.uint32):
-                raise TypeError("px/py must be int32 or uint32 tensors")
-        px, py = px.contiguous().reshape(-1), py.contiguous().reshape(-1)
-        if px.shape[0] != py.shape[0]:
-            raise ValueError("px and py lengths differ")
-        n = px.shape[0]
-        hits = torch.empty((n, 16), dtype=torch.int32, device=px.device)
-        if n:
-            check(lib().vr_pick(*args, c_void_p(px.data_ptr()), c_void_p(py.data_ptr()), n, 1,
-                                c_void_p(hits.data_ptr()), 1, sp), "vr_pick")
-        return hits
-    px = np.ascontiguousarray(px, dtype=np.uint32).reshape(-1)
-    py = np.ascontiguousarray(py, dtype=np.uint32).reshape(-1)
-    if px.shape[0] != py.shape[0]:
-        raise ValueError("px and py lengths differ")
-    n = px.shape[0]
-    hits = np.zeros(n, dtype=HIT_DTYPE)
+    px, py, n, dev = _pixel_lists(px, py)
+    hits = _records(n, HIT_DTYPE, px)
     if n:
-        check(lib().vr_pick(*args, px.ctypes.data_as(c_void_p), py.ctypes.data_as(c_void_p), n, 0,
-                            hits.ctypes.data_as(c_void_p), 0, sp), "vr_pick")
+        check(lib().vr_pick(*args, _ptr(px), _ptr(py), n, dev, _ptr(hits), dev, _stream_ptr(stream)), "vr_pick")
     return hits
 
 
@@ -535,6 +547,17 @@ def _rays_numpy(rays) -> np.ndarray:
     return out
 
 
+def _rays_cuda(rays):
+    """An (n, 8) contiguous float32 CUDA tensor, the bytes of vr_ray, from one or from an (n, 6) tensor."""
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] not in (6, 8):
+        raise TypeError("rays must be a float32 CUDA tensor of shape (n, 8) or (n, 6)")
+    if rays.shape[1] == 6:
+        full = torch.zeros((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+        full[:, 0:3], full[:, 4:7] = rays[:, 0:3], rays[:, 3:6]
+        rays = full
+    return rays.contiguous()
+
+
 def trace(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, rays,
           order: TraceOrder = TraceOrder.AUTO, stream=None):
     """vr_trace: the closest hit of each ray -- the record pick() gives for a pixel, for rays that
@@ -546,28 +569,13 @@ def trace(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo
     execution order only, never a record.  A zero, NaN or infinite ray gets the record the
     reference's walk gives it.  Runs on `stream` (default: the current stream) and returns when
     the records are written."""
-    sp = _stream_ptr(stream)
     args = (scene.handle, int(algorithm), f3(info.translation), int(info.scale))
-    if hasattr(rays, "is_cuda") and rays.is_cuda:
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] not in (6, 8):
-            raise TypeError("rays must be a float32 CUDA tensor of shape (n, 8) or (n, 6)")
-        if rays.shape[1] == 6:
-            full = torch.zeros((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
-            full[:, 0:3], full[:, 4:7] = rays[:, 0:3], rays[:, 3:6]
-            rays = full
-        rays = rays.contiguous()
-        n = rays.shape[0]
-        hits = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
-        if n:
-            check(lib().vr_trace(*args, c_void_p(rays.data_ptr()), n, 1, c_void_p(hits.data_ptr()), 1, int(order), sp),
-                  "vr_trace")
-        return hits
-    rays = _rays_numpy(rays)
+    dev = hasattr(rays, "is_cuda") and rays.is_cuda
+    rays = _rays_cuda(rays) if dev else _rays_numpy(rays)
     n = rays.shape[0]
-    hits = np.zeros(n, dtype=HIT_DTYPE)
+    hits = _records(n, HIT_DTYPE, rays)
     if n:
-        check(lib().vr_trace(*args, rays.ctypes.data_as(c_void_p), n, 0, hits.ctypes.data_as(c_void_p), 0, int(order),
-                             sp), "vr_trace")
+        check(lib().vr_trace(*args, _ptr(rays), n, dev, _ptr(hits), dev, int(order), _stream_ptr(stream)), "vr_trace")
     return hits
 
 
@@ -577,32 +585,12 @@ def camera_rays(camera: Camera, width: int, height: int, px, py, device: int = 0
     normalised, so trace(camera_rays(px, py)) has the bytes of pick(px, py) for pixels inside the
     frame; a pixel outside it gets an all-NaN ray.  numpy (or list) px/py give a numpy RAY_DTYPE
     array; CUDA int32/uint32 tensors give an (n, 8) float32 CUDA tensor of the same bytes."""
-    sp = _stream_ptr(stream)
     args = (int(device), ctypes.byref(camera.raw), int(width), int(height))
-    if hasattr(px, "is_cuda") and px.is_cuda:
-        if not (hasattr(py, "is_cuda") and py.is_cuda) or px.device != py.device:
-            raise TypeError("px and py must both be CUDA tensors on one device")
-        for t in (px, py):
-            if t.dtype not in (torch.int32, torch.uint32):
-                raise TypeError("px/py must be int32 or uint32 tensors")
-        px, py = px.contiguous().reshape(-1), py.contiguous().reshape(-1)
-        if px.shape[0] != py.shape[0]:
-            raise ValueError("px and py lengths differ")
-        n = px.shape[0]
-        rays = torch.empty((n, 8), dtype=torch.float32, device=px.device)
-        if n:
-            check(lib().vr_camera_rays(*args, c_void_p(px.data_ptr()), c_void_p(py.data_ptr()), n, 1,
-                                       c_void_p(rays.data_ptr()), 1, sp), "vr_camera_rays")
-        return rays
-    px = np.ascontiguousarray(px, dtype=np.uint32).reshape(-1)
-    py = np.ascontiguousarray(py, dtype=np.uint32).reshape(-1)
-    if px.shape[0] != py.shape[0]:
-        raise ValueError("px and py lengths differ")
-    n = px.shape[0]
-    rays = np.zeros(n, dtype=RAY_DTYPE)
+    px, py, n, dev = _pixel_lists(px, py)
+    rays = _records(n, RAY_DTYPE, px)
     if n:
-        check(lib().vr_camera_rays(*args, px.ctypes.data_as(c_void_p), py.ctypes.data_as(c_void_p), n, 0,
-                                   rays.ctypes.data_as(c_void_p), 0, sp), "vr_camera_rays")
+        check(lib().vr_camera_rays(*args, _ptr(px), _ptr(py), n, dev, _ptr(rays), dev, _stream_ptr(stream)),
+              "vr_camera_rays")
     return rays
 
 
