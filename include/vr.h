@@ -279,6 +279,44 @@ int vr_trace(const vr_scene* s, vr_algo algo, const float translation[3], uint32
              const vr_ray* rays, size_t n, int inputs_on_device,
              vr_hit* hits, int outputs_on_device, uint32_t order, void* stream);
 
+/* Lit colours, and on request hits, for arbitrary rays: colors[i] is the packed 0x00RRGGBB word
+ * vr_render writes for a pixel whose ray is rays[i] -- applyLighting at the primary hit
+ * (Renderer.cuh:249-258), times !shadow when lit->use_shadows.  The primary walk is vr_trace's,
+ * bit for bit (from (origin - translation) * scale along makeUnitVector(direction), correctly
+ * rounded sqrt and divisions); the shadow walk is the render's, from the hit's point in the
+ * hit's region towards the light.  A miss gives 0; so does a primary or a shadow walk the
+ * reference would never finish, which is what the render writes.  With vr_camera_rays' rays
+ * of a frame's pixels the colours are that frame's render, word for word: any other set of
+ * rays (a mirror bounce from a hit's point, an orthographic, fisheye or stereo view, a
+ * jittered sample pattern, a light probe) gets what that render would have given it.
+ *
+ * hits (may be NULL): when given, hits[i] is byte for byte the record vr_trace writes for
+ * rays[i], from the same walk -- a bounce ray's origin, normal and colour in one call.  Its
+ * status is VR_HIT_NEVER only for a PRIMARY walk that never ends; a shadow walk that never
+ * ends leaves the primary's VOXEL record beside colour 0.  The colours are the same words
+ * with and without it.
+ *
+ * No ray is rejected (as vr_trace) and no lighting value is: light_dir is taken as plain data,
+ * as vr_render takes it.  order is a vr_trace_order with vr_trace's meaning: the execution
+ * order only, never a word or a record; AUTO is GIVEN.
+ *
+ * rays: n records, on the scene's device (16-byte aligned) when inputs_on_device != 0; colors
+ * (n words, 4-byte aligned) and hits (n records, 16-byte aligned) both on the device when
+ * outputs_on_device != 0, both on the host otherwise.  Host arrays are staged through device
+ * buffers the call allocates and frees; GIVEN with everything on the device allocates
+ * nothing.  The work runs on `stream` and the call returns when the outputs are written.
+ * n == 0 returns VR_OK and does nothing.  As a trace, a shade is not a render launch: no ring
+ * slot, nothing learned or forgotten.
+ *
+ * VR_E_INVALID (nothing is written): s, lit or translation NULL; rays or colors NULL with
+ * n > 0; n >= 2^31; an unknown algorithm; an unknown order; a misaligned device array; a
+ * stream that is capturing a HIP graph. */
+int vr_shade(const vr_scene* s, vr_algo algo, const vr_lighting* lit,
+             const float translation[3], uint32_t scale,
+             const vr_ray* rays, size_t n, int inputs_on_device,
+             uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
+             uint32_t order, void* stream);
+
 /* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
  * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
  * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the

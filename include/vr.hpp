@@ -172,6 +172,23 @@ inline std::vector<vr_hit> trace(RayMarchAlgorithm algo, const VoxelSceneInfo& i
     return hits;
 }
 
+// vr_shade: the colour runRaymarchingKernel writes for a pixel whose ray is rays[i] (0x00RRGGBB:
+// lit, and shadowed when lighting.use_shadows; 0 for a miss) -- for rays that are no pixel of a
+// camera.  hits (optional): filled with the records trace() gives for the same rays, from the
+// same walk.  Host arrays in, host arrays out; returns when they are written.
+inline std::vector<uint32_t> shade(RayMarchAlgorithm algo, const VoxelSceneInfo& info, const vr_lighting& lighting,
+                                   const DeviceScene& scene, const std::vector<vr_ray>& rays,
+                                   std::vector<vr_hit>* hits = nullptr, vr_trace_order order = VR_TRACE_ORDER_AUTO,
+                                   void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> colors(rays.size());
+    if (hits) hits->assign(rays.size(), vr_hit{});
+    check(vr_shade(scene.get(), (vr_algo)algo, &lighting, t, info.scale, rays.data(), rays.size(), 0, colors.data(),
+                   hits ? hits->data() : nullptr, 0, (uint32_t)order, stream),
+          "shade");
+    return colors;
+}
+
 // vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
 // frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
 inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,

@@ -128,6 +128,8 @@ SIGNATURES = {
                         c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
     "vr_trace": (c_int, [c_void_p, c_int, POINTER(c_float), c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_int,
                          c_uint32, c_void_p]),
+    "vr_shade": (c_int, [c_void_p, c_int, POINTER(VrLighting), POINTER(c_float), c_uint32, c_void_p, c_size_t, c_int,
+                         c_void_p, c_void_p, c_int, c_uint32, c_void_p]),
     "vr_camera_rays": (c_int, [c_int, POINTER(VrCamera), c_uint32, c_uint32, c_void_p, c_void_p, c_size_t, c_int,
                                c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),

@@ -16,6 +16,10 @@
 //                                 voxel, colour, normal and hit point it reaches from world origin
 //                                 O in direction D (any length) -- vr_trace, with the scale above
 //                                 and a zero translation; not with --gpus N > 1)
+//                   [--shade OX,OY,OZ,DX,DY,DZ]...  (after the traces: one line per ray with the colour
+//                                 the render would give it -- vr_shade, with the run's scale and
+//                                 lighting flags and a zero translation -- then the --trace text
+//                                 of its hit; not with --gpus N > 1)
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -115,6 +119,7 @@ int main(int argc, char* argv[]) {
     bool shadows = true, point_light = false, has_dir = false;
     std::vector<uint32_t> pick_x, pick_y;    // --pick X,Y (repeatable)
     std::vector<vr_ray> trace_rays;          // --trace OX,OY,OZ,DX,DY,DZ (repeatable)
+    std::vector<vr_ray> shade_rays;          // --shade OX,OY,OZ,DX,DY,DZ (repeatable)
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -156,11 +161,19 @@ int main(int argc, char* argv[]) {
             }
             trace_rays.push_back(ray);
         }
+        else if (a == "--shade") {
+            vr_ray ray;
+            if (!parse_ray(next("--shade"), ray)) {
+                std::cerr << "--shade needs OX,OY,OZ,DX,DY,DZ" << std::endl;
+                std::exit(2);
+            }
+            shade_rays.push_back(ray);
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
-                         "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]..." << std::endl;
+                         "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]..." << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -180,6 +193,10 @@ int main(int argc, char* argv[]) {
     }
     if (!trace_rays.empty() && multi && gpus > 1) {
         std::cerr << "ERROR: --trace is a single-GPU query: not with --gpus " << gpus << std::endl;
+        return 2;
+    }
+    if (!shade_rays.empty() && multi && gpus > 1) {
+        std::cerr << "ERROR: --shade is a single-GPU query: not with --gpus " << gpus << std::endl;
         return 2;
     }
     // argv[1] = scale (Main.cu:181-186); optional here (README.md:22-25 omits it).
@@ -250,17 +267,31 @@ int main(int argc, char* argv[]) {
         lit.use_shadows = shadows;                               // Main.cu:40
 
         // --trace: the closest hit of each given ray (vr_trace), printed after the picks
+        auto print_record = [](const vr_hit& h) {      // (the rest of a --trace or --shade line)
+            if (h.status == VR_HIT_VOXEL)
+                std::printf("voxel %d %d %d color 0x%06X normal %d %d %d point %.9g %.9g %.9g\n", h.voxel[0], h.voxel[1],
+                            h.voxel[2], h.color, h.normal[0], h.normal[1], h.normal[2], h.point[0], h.point[1], h.point[2]);
+            else
+                std::printf("%s\n", h.status == VR_HIT_MISS ? "miss" : "never");
+        };
         auto print_traces = [&]() {
             if (trace_rays.empty()) return;
             const std::vector<vr_hit> hits = vrx::trace(algo, sinfo, scene, trace_rays);
             for (size_t i = 0; i < hits.size(); ++i) {
-                const vr_hit& h = hits[i];
-                if (h.status == VR_HIT_VOXEL)
-                    std::printf("trace %zu voxel %d %d %d color 0x%06X normal %d %d %d point %.9g %.9g %.9g\n", i, h.voxel[0],
-                                h.voxel[1], h.voxel[2], h.color, h.normal[0], h.normal[1], h.normal[2], h.point[0],
-                                h.point[1], h.point[2]);
-                else
-                    std::printf("trace %zu %s\n", i, h.status == VR_HIT_MISS ? "miss" : "never");
+                std::printf("trace %zu ", i);
+                print_record(hits[i]);
+            }
+            std::fflush(stdout);
+        };
+        // --shade: the colour the render would give each given ray, and its hit (vr_shade, with
+        // the run's lighting), printed after the traces
+        auto print_shades = [&]() {
+            if (shade_rays.empty()) return;
+            std::vector<vr_hit> hits;
+            const std::vector<uint32_t> colors = vrx::shade(algo, sinfo, lit, scene, shade_rays, &hits);
+            for (size_t i = 0; i < colors.size(); ++i) {
+                std::printf("shade %zu color 0x%06X ", i, colors[i]);
+                print_record(hits[i]);
             }
             std::fflush(stdout);
         };
@@ -304,6 +335,7 @@ int main(int argc, char* argv[]) {
                           << " microseconds" << std::endl;
             print_picks();                   // (--gpus 1: the scene of this process's device)
             print_traces();
+            print_shades();
             std::vector<uint8_t> host;
             if (!mg.download(host)) {
                 std::cerr << "ERROR: " << mg.error() << std::endl;
@@ -338,6 +370,7 @@ int main(int argc, char* argv[]) {
                   << " microseconds (" << (double)width * height / (best_ms * 1e3) << " Mrays/s)" << std::endl;
         print_picks();
         print_traces();
+        print_shades();
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,
         // async copy into pinned memory, parallel PNG encode (vr_png_write).
         const size_t nbytes = (size_t)width * height * 3;

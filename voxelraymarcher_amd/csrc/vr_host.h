@@ -90,8 +90,11 @@ int build_scene(int device, vr_store store, const int32_t* xyz, const uint32_t* 
                 vr_build mode, void* stream, vr_scene** out);
 
 // vr_launch.cpp: the camera and frame size of a view (v.W, v.H, v.LW; nothing else is written),
-// and the whole view of a render (zeroed first; the launch's rows and tile deal are the caller's)
+// its lighting block (L, LC, LP, Lr, L_fast, Lw, L_order, L_cls, L_unit, L_eq and the two flags;
+// nothing else is written), and the whole view of a render (zeroed first; the launch's rows and
+// tile deal are the caller's)
 void view_camera(KView& v, const vr_camera* cam, uint32_t width, uint32_t height);
+void view_lighting(KView& v, const vr_lighting* lit);
 int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, const float translation[3],
               uint32_t scale, uint32_t width, uint32_t height, KView& v);
 

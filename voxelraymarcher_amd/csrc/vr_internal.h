@@ -1,5 +1,5 @@
 // vr_internal.h -- layouts shared by the host builder (vr_scene.cpp) and the
-// HIP kernels (vr_march.hip, vr_order.hip, vr_query.hip, vr_util.hip; the walker: vr_walk.h).  See DESIGN.md "Data layout in HBM".
+// HIP kernels (vr_march.hip, vr_order.hip, vr_query.hip, vr_shade.hip, vr_util.hip; the walker: vr_walk.h).  See DESIGN.md "Data layout in HBM".
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -197,6 +197,11 @@ hipError_t launch_pick(int store, int algo, const KScene& s, const KView& v, con
 // view only translation and scale_f are read.
 hipError_t launch_trace(int store, int algo, const KScene& s, const KView& v, const void* rays, const uint32_t* idx,
                         uint32_t n, void* hits, hipStream_t stream);
+// vr_shade's kernel (vr_shade.hip): the render's colour for each of n rays (vr_ray records and idx
+// as for launch_trace), one 4-byte word per ray in colors; hits (or null): launch_trace's records
+// too, from the same walk.  Of the view the lighting block, translation and scale_f are read.
+hipError_t launch_shade(int store, int algo, const KScene& s, const KView& v, const void* rays, const uint32_t* idx,
+                        uint32_t n, uint32_t* colors, void* hits, hipStream_t stream);
 // vr_camera_rays' kernel: the rays of pixels (px[i], py[i]) of the view's frame (one band over it).
 hipError_t launch_camera_rays(const KView& v, const uint32_t* px, const uint32_t* py, uint32_t n, void* rays,
                               hipStream_t stream);

@@ -1,7 +1,8 @@
 // vr_launch.cpp -- the render launch: the per-device slot ring, the learned orders and the
 // crawl-pass skip kept per slot (their decisions: vr_launch_plan.h), the render entry points of
-// include/vr.h with the view they render (make_view; vr_query_api.cpp's pick shares it and
-// nothing else), the band and tile helpers and the vr_debug_* functions.
+// include/vr.h with the view they render (make_view; vr_query_api.cpp's pick shares it, its
+// shade the lighting block, view_lighting, and nothing else), the band and tile helpers and the
+// vr_debug_* functions.
 //
 // Replaces runRaymarchingKernel (main/Main.cu:105-163).
 #include <algorithm>
@@ -34,16 +35,9 @@ void view_camera(KView& v, const vr_camera* cam, uint32_t width, uint32_t height
     v.LW = width;
 }
 
-int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, const float translation[3],
-              uint32_t scale, uint32_t width, uint32_t height, KView& v) {
-    if (!s) return fail(VR_E_INVALID, "scene is NULL");
-    if (!cam || !lit) return fail(VR_E_INVALID, "camera/lighting NULL");
-    if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "bad image size");
-    memset(&v, 0, sizeof v);
-    view_camera(v, cam, width, height);
+void view_lighting(KView& v, const vr_lighting* lit) {
     for (int i = 0; i < 3; ++i) {
         v.L[i] = lit->light_dir[i]; v.LC[i] = lit->light_color[i]; v.LP[i] = lit->light_pos[i];
-        v.translation[i] = translation ? translation[i] : 0.0f;
     }
     v.L_fast = 1u;
     for (int i = 0; i < 3; ++i) {
@@ -69,9 +63,20 @@ int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, c
         v.L_unit = unit ? 1u : 0u;
         v.L_eq = (v.L[0] == v.L[1] && v.L[1] == v.L[2]) ? 1u : 0u;
     }
-    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
     v.use_point_light = lit->use_point_light ? 1 : 0;
     v.use_shadows = lit->use_shadows ? 1 : 0;
+}
+
+int make_view(const vr_scene* s, const vr_camera* cam, const vr_lighting* lit, const float translation[3],
+              uint32_t scale, uint32_t width, uint32_t height, KView& v) {
+    if (!s) return fail(VR_E_INVALID, "scene is NULL");
+    if (!cam || !lit) return fail(VR_E_INVALID, "camera/lighting NULL");
+    if (width == 0 || height == 0 || width > 65536 || height > 65536) return fail(VR_E_INVALID, "bad image size");
+    memset(&v, 0, sizeof v);
+    view_camera(v, cam, width, height);
+    view_lighting(v, lit);
+    for (int i = 0; i < 3; ++i) v.translation[i] = translation ? translation[i] : 0.0f;
+    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
     return VR_OK;
 }
 

@@ -102,30 +102,7 @@ __device__ __forceinline__ uint32_t* tile_prim() {
     return p;
 }
 
-// applyLighting at the primary hit (Renderer.cuh:249-258; regionWorldPosition :413)
-// times !shadow (:315,737,821): the pixel's colour.
-// (ALGO: the original algorithm's kernels take the shadow walk's sign arms, Walker::shadow)
-template <int ALGO, int STORE, bool COUNT, bool CRAWL>
-__device__ __forceinline__ uint32_t light_and_shadow(Walker<STORE, COUNT, CRAWL>& w, const KView& v, const Hit& h) {
-    constexpr bool kArms = ALGO == ALGO_ORIGINAL;
-    bool sh = false;
-    const f3 rwp = add(ld3(v.translation), mk((float)(h.region.x * kBlock), (float)(h.region.y * kBlock),
-                                              (float)(h.region.z * kBlock)));
-    const uint32_t lit = w.lighting(h.col, h.nc, rwp, h.so);
-    if (v.use_shadows) {
-        VR_DIAG_COUNT(16);                             // shadow walks started
-        w.lit_saved = lit;
-        const bool eq = v.L[0] == v.L[1] && v.L[1] == v.L[2];
-        if (h.longest) {
-            w.ctx = 2u;
-            sh = w.template shadow<true>(h.so, h.region);
-        } else {
-            sh = eq ? w.template shadow<false, true, kArms>(h.so, h.region)
-                    : w.template shadow<false, false, kArms>(h.so, h.region);
-        }
-    }
-    return lit * (uint32_t)!sh;
-}
+// (light_and_shadow, the pixel's colour at a primary hit: vr_walk.h -- vr_shade.hip's kernel shares it)
 
 // Tile pass: hand this lane's pixel (tile_pixels) to the crawl pass, to be walked there
 // from its start (a record with flag 4).  Returns what the tile pass writes for

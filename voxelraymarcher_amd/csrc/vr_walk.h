@@ -1,6 +1,6 @@
 // vr_walk.h -- the Walker: both grid walks, the VCS longest-axis walk, primary and shadow,
-// and pixel_ray.  Included by every unit that walks a ray: vr_march.hip (the tile and crawl
-// passes) and vr_query.hip (pick and trace).
+// light_and_shadow (a hit's colour) and pixel_ray.  Included by every unit that walks a ray:
+// vr_march.hip (the tile and crawl passes), vr_query.hip (pick and trace) and vr_shade.hip.
 //
 // Arithmetic follows the reference expression by expression (file:line in
 // each function) under the FP policy of SURVEY.md 8(c): -ffp-contract=off,
@@ -9,12 +9,13 @@
 //
 // With the walker come the few things the tile pass's walker needs from the render path:
 // kDeferredIters, deferral_report, tile_pixels and the deferral write inside
-// grid_original_rt (compiled out for CRAWL = true, which is all vr_query.hip instantiates).
+// grid_original_rt (compiled out for CRAWL = true, which is all vr_query.hip and vr_shade.hip
+// instantiate).
 //
 // The counting macros VR_DIAG_COUNT, VR_DIAG_COUNT_IF and VR_DIAG_PAT are no-ops here unless
 // the including unit defined them first.  Only vr_march.hip does (g_vr_diag lives there): in
 // the counting build libvr_cover.so the tile and crawl passes count, the pick and trace
-// kernels of vr_query.hip do not.
+// kernels of vr_query.hip and the shade kernel of vr_shade.hip do not.
 #pragma once
 #include "vr_device.h"
 #include "vr_crawl.h"        // crawl_steps, crawl_run, crawl_voxel
@@ -1414,6 +1415,32 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
         return false;
     }
 };
+
+// applyLighting at the primary hit (Renderer.cuh:249-258; regionWorldPosition :413)
+// times !shadow (:315,737,821): the pixel's colour.
+// (ALGO: the original algorithm's kernels take the shadow walk's sign arms, Walker::shadow)
+// W: any Walker -- the render's (vr_march.hip) or, with PICK, the shade kernel's (vr_shade.hip).
+template <int ALGO, class W>
+__device__ __forceinline__ uint32_t light_and_shadow(W& w, const KView& v, const Hit& h) {
+    constexpr bool kArms = ALGO == ALGO_ORIGINAL;
+    bool sh = false;
+    const f3 rwp = add(ld3(v.translation), mk((float)(h.region.x * kBlock), (float)(h.region.y * kBlock),
+                                              (float)(h.region.z * kBlock)));
+    const uint32_t lit = w.lighting(h.col, h.nc, rwp, h.so);
+    if (v.use_shadows) {
+        VR_DIAG_COUNT(16);                             // shadow walks started
+        w.lit_saved = lit;
+        const bool eq = v.L[0] == v.L[1] && v.L[1] == v.L[2];
+        if (h.longest) {
+            w.ctx = 2u;
+            sh = w.template shadow<true>(h.so, h.region);
+        } else {
+            sh = eq ? w.template shadow<false, true, kArms>(h.so, h.region)
+                    : w.template shadow<false, false, kArms>(h.so, h.region);
+        }
+    }
+    return lit * (uint32_t)!sh;
+}
 
 // calculateWorldRay (Renderer.cuh:1013-1022) + Camera::generateRay (Camera.cuh:25-29)
 // for pixel (x, local row l); false when the row is outside the frame.

@@ -174,6 +174,11 @@ class DeviceScene:
         """vr_trace with this scene: see trace()."""
         return trace(self, algorithm, info, rays, order=TraceOrder.AUTO if order is None else order, stream=stream)
 
+    def shade(self, algorithm, info, lighting, rays, order=None, hits: bool = False, stream=None):
+        """vr_shade with this scene: see shade()."""
+        return shade(self, algorithm, info, lighting, rays, order=TraceOrder.AUTO if order is None else order,
+                     hits=hits, stream=stream)
+
     def close(self) -> None:
         if self._h:
             lib().vr_scene_destroy(self._h)
@@ -577,6 +582,28 @@ def trace(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo
     if n:
         check(lib().vr_trace(*args, _ptr(rays), n, dev, _ptr(hits), dev, int(order), _stream_ptr(stream)), "vr_trace")
     return hits
+
+
+def shade(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, lighting: _capi.VrLighting, rays,
+          order: TraceOrder = TraceOrder.AUTO, hits: bool = False, stream=None):
+    """vr_shade: the colour a render writes for a pixel whose ray is rays[i] -- lit as the render
+    lights it and, with lighting.use_shadows, shadowed by the render's shadow walk; 0 for a miss
+    and for a walk the reference would never finish.  shade(camera_rays(...)) of a frame's pixels
+    is that frame's render, word for word.  The ray forms are trace()'s.  numpy rays give a uint32
+    numpy array of n words (0x00RRGGBB); a CUDA tensor gives an int32 CUDA tensor of shape (n,)
+    with the same bits.  hits=True returns (colours, records), the records as trace() returns
+    them and from the same walk.  `order` changes the execution order only.  Runs on `stream`
+    (default: the current stream) and returns when the outputs are written."""
+    args = (scene.handle, int(algorithm), ctypes.byref(lighting), f3(info.translation), int(info.scale))
+    dev = hasattr(rays, "is_cuda") and rays.is_cuda
+    rays = _rays_cuda(rays) if dev else _rays_numpy(rays)
+    n = rays.shape[0]
+    colors = torch.empty(n, dtype=torch.int32, device=rays.device) if dev else np.zeros(n, dtype=np.uint32)
+    recs = _records(n, HIT_DTYPE, rays) if hits else None
+    if n:
+        check(lib().vr_shade(*args, _ptr(rays), n, dev, _ptr(colors), _ptr(recs) if hits else None, dev, int(order),
+                             _stream_ptr(stream)), "vr_shade")
+    return (colors, recs) if hits else colors
 
 
 def camera_rays(camera: Camera, width: int, height: int, px, py, device: int = 0, stream=None):
