@@ -509,6 +509,23 @@ int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t 
  * that has not rendered, [0..5] are 0.  VR_E_INVALID for a NULL out or a device outside 0..63.
  * Never needed by a renderer. */
 int vr_debug_order_uses(int device, uint64_t out[8]);
+/* Test hook: while `on` is nonzero every render launch of the device plans as if another
+ * stream's launch were running on it ("frames in flight": vr_schedule AUTO keeps grid order,
+ * vr_occupancy AUTO takes the in-flight variant, the crawl pass takes its in-flight records per
+ * wave), whatever the device is really doing.  Sticky until turned off with on = 0; nothing else
+ * about a launch changes, and no pixel does.  Host state only: never initialises the device.
+ * VR_E_INVALID for a device outside 0..63.  Never needed by a renderer. */
+int vr_debug_force_in_flight(int device, int on);
+/* Test hook: what the device's most recent render launch that reached the tile pass decided.
+ * out[0] whether it planned as alone (no other stream's launch running), [1] whether its tile
+ * pass dispatched heaviest first (a work order used or learned), [2] whether it took the
+ * in-flight occupancy variant, [3] the crawl pass's records per wave, [4] the crawl pass's grid
+ * in workgroups, [5] whether its crawl pass ran (0: skipped), [6] the record count that the
+ * device's last completed crawl pass reported -- a hint the next launch sizes its grid by;
+ * read it after waiting for the launch -- [7] 0.  Reads host state only and never initialises
+ * the device: all 0 for a device that has not rendered.  VR_E_INVALID for a NULL out or a
+ * device outside 0..63.  Never needed by a renderer. */
+int vr_debug_last_launch(int device, uint64_t out[8]);
 /* Every vr_render* call returns VR_E_INVALID on a stream that is capturing a HIP graph
  * (its per-device slot ring and work-order bookkeeping are host state that a graph replay
  * would not repeat). */

@@ -156,6 +156,10 @@ struct SlotRing {
         uint32_t last_idx = 0;
         uint64_t last_key = 0;             // the view of the device's previous launch
         bool force_skip = false;           // vr_debug_skip_next_crawl (tests)
+        bool force_in_flight = false;      // vr_debug_force_in_flight (tests): launches plan as not alone
+        // vr_debug_last_launch (tests): the plan of the device's latest render launch -- alone,
+        // heavy, hi, crawl_rpw, the crawl pass's grid, whether the crawl pass ran
+        uint32_t last_plan[6] = {0, 0, 0, 0, 0, 0};
         // vr_debug_order_uses (tests): render launches, lane orders made, launches with a lane
         // order bound, work orders made, launches with a work order bound, crawl passes skipped
         uint64_t uses[6] = {0, 0, 0, 0, 0, 0};
@@ -446,7 +450,7 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
     uint32_t gx = 0, gy = 0;
     vr::march_grid(v, gx, gy);
     const uint32_t n = gx * gy;
-    const bool alone = D.alone(st);
+    const bool alone = D.alone(st) && !D.force_in_flight;
     VR_HP(2);
     const vr::LaunchPolicy pol = vr::launch_policy(schedule, occupancy, alone, policy_knobs());
     v.crawl_rpw = pol.crawl_rpw;
@@ -477,6 +481,8 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
     D.uses[2] += v.perm != nullptr;
     D.uses[4] += v.order != nullptr;
     D.uses[5] += !crawl;
+    const uint32_t plan[6] = {alone, pol.heavy, pol.hi, v.crawl_rpw, cwgs, crawl};
+    std::memcpy(D.last_plan, plan, sizeof plan);
     VR_HP(6);
     e = vr::launch_march((int)s->store, (int)algo, v.bytes != nullptr, ks, v, st, cwgs, pol.hi, crawl);
     VR_HP(7);
@@ -653,6 +659,26 @@ int vr_debug_order_uses(int device, uint64_t out[8]) {
     for (int i = 0; i < 6; ++i) out[i] = D.uses[i];
     out[6] = g_defer_ring.nslots;
     out[7] = (uint64_t)sh.block_x << 16 | sh.block_y;
+    return VR_OK;
+}
+
+int vr_debug_force_in_flight(int device, int on) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    D.force_in_flight = on != 0;
+    return VR_OK;
+}
+
+int vr_debug_last_launch(int device, uint64_t out[8]) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    if (!out) return fail(VR_E_INVALID, "out is NULL");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    for (int i = 0; i < 6; ++i) out[i] = D.last_plan[i];
+    // (host-mapped: written by the device's last completed crawl pass; none before the ring exists)
+    out[6] = D.stat_host ? *(volatile uint32_t*)D.stat_host : 0u;
+    out[7] = 0;
     return VR_OK;
 }
 

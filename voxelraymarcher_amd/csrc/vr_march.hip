@@ -122,14 +122,17 @@ __device__ __forceinline__ uint32_t defer_rewalk(const KView& v) {
     return kDeferMarker;
 }
 
-// The crawl pass's LDS for one record lane: its cluster-bit slot.
+// The crawl pass's cluster bits for one record lane: its LDS slot, or (no slot: more records
+// per wave than kCrawlMaxRpw) the scene's bits in memory for the crawls' closed form alone.
 struct CrawlLds {
     uint32_t* lbm = nullptr;
+    bool mem = false;
 };
 template <class W>
 __device__ __forceinline__ void attach(W& w, const CrawlLds* cl) {
     if (!cl) return;
     w.lbm = cl->lbm;
+    w.mem_bits = cl->mem;
 }
 
 // The body of rayMarchSceneOriginal / rayMarchSceneJumpAxis (Renderer.cuh:1033-1063)
@@ -344,15 +347,19 @@ __global__ __launch_bounds__(64 * kCrawlWaves) void crawl_kernel(KScene s, KView
     // kCrawlRpw records per wave at a time (lanes 0 .. kCrawlRpw-1): each record is a long
     // chain of dependent iterations, and the lanes of a wave take different paths through
     // the walk, so fewer lanes per wave -- spread over more waves -- finish sooner
-    // (v.crawl_rpw: the host's choice per launch -- 4 for a lone frame, whose time is the
-    // longest record's chain; 8 with frames in flight, where the pass's issue cycles count:
-    // C5 0.6707 -> 0.6514 ms per frame, profiles/r03/rpw_deep/; 32 since round 6, never slower
-    // and in some runs 4 % faster, vr_launch_plan.h launch_policy)
+    // (v.crawl_rpw: the host's choice per launch, vr_launch_plan.h launch_policy -- 2 for a
+    // lone frame, whose time is the longest record's chain; VR_CRAWL_RPW_IN_FLIGHT, 32 by
+    // default, with frames in flight, where the pass's issue cycles count; VR_CRAWL_RPW = 1..64
+    // for every launch.  Above kCrawlMaxRpw no lane has an LDS slot: every skip step loads,
+    // and the crawls' closed form reads the cluster bits from memory.
+    // Round 3 ran 4 and 8: C5 0.6707 -> 0.6514 ms per frame in flight, profiles/r03/rpw_deep/)
     const uint32_t rpw = v.crawl_rpw ? v.crawl_rpw : kCrawlRpw;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, wlane = threadIdx.x & 63u;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    if (STORE == STORE_VCS && s.vcs_cbits && rpw <= kCrawlMaxRpw && wlane < rpw)
-        cl.lbm = dyn + 4 + ((threadIdx.x >> 6) * kCrawlMaxRpw + wlane) * 16u;
+    if (STORE == STORE_VCS && s.vcs_cbits && wlane < rpw) {
+        if (rpw <= kCrawlMaxRpw) cl.lbm = dyn + 4 + ((threadIdx.x >> 6) * kCrawlMaxRpw + wlane) * 16u;
+        else cl.mem = true;
+    }
     for (uint32_t i = wave * rpw + wlane; wlane < rpw && i < n; i += nwaves * rpw) {
         uint32_t* r = v.defer + 4 + (size_t)i * kDeferRecWords;
         // (a record of another launch -- one whose crawl pass the host skipped, believing its

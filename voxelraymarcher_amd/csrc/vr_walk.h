@@ -161,6 +161,11 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
     // clusters: a skip step reads one LDS word instead.
     uint32_t* lbm = nullptr;
     uint32_t bm_reg = kNone;
+    // Crawl pass (VCS) at more records per wave than it has LDS slots (lbm null): the walk
+    // loop loads every mask word, but a crawl's closed form (crawl_run) still crosses the
+    // faces of absent clusters, reading the region's bits from memory -- the same iterations
+    // are fast-forwarded at every width.
+    bool mem_bits = false;
 
     // rayMarchVoxelGrid (Renderer.cuh:260-336) and, SHADOW, shadowRayMarchVoxelGrid (:100-172).
     // The cluster-skip step (:290-306) and the voxel step (:318-331) share one
@@ -267,6 +272,10 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                     }
                     bits = lbm;
                 }
+            }
+            const uint32_t* run_bits = bits;       // crawl_run's
+            if constexpr (CRAWL) {
+                if (!bits && mem_bits) run_bits = s.vcs_cbits + (size_t)reg * 16u;
             }
             // Straight-line body with one exit: the hit test, the region test of
             // the stepped position and the iteration budget are folded into a
@@ -559,9 +568,9 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                     // Off the hot loop: fast-forward the identical crawl iterations
                     // exactly, then resume the walk (no region-entry step).
 #ifdef VR_CRAWL_PROF
-                    const uint32_t n = crawl_run(o, d, qx, qy, qz, px, py, pz, kBudget - this->iters, bits, &this->d_trips);
+                    const uint32_t n = crawl_run(o, d, qx, qy, qz, px, py, pz, kBudget - this->iters, run_bits, &this->d_trips);
 #else
-                    const uint32_t n = crawl_run(o, d, qx, qy, qz, px, py, pz, kBudget - this->iters, bits);
+                    const uint32_t n = crawl_run(o, d, qx, qy, qz, px, py, pz, kBudget - this->iters, run_bits);
 #endif
                     // none (not a real crawl, or its next step leaves the cluster): a few plain
                     // iterations, then re-arm

@@ -697,6 +697,25 @@ def debug_order_uses(device: int = 0) -> dict:
     return d
 
 
+def debug_force_in_flight(device: int = 0, on: bool = True) -> None:
+    """Test hook (vr_debug_force_in_flight): while on, every launch of the device plans as if
+    another stream's launch were running on it; sticky until turned off."""
+    check(lib().vr_debug_force_in_flight(int(device), int(bool(on))), "vr_debug_force_in_flight")
+
+
+LAST_LAUNCH = ("alone", "heavy", "hi", "crawl_rpw", "crawl_grid", "crawl_ran", "records")
+
+
+def debug_last_launch(device: int = 0) -> dict:
+    """Test hook (vr_debug_last_launch): what the device's most recent render launch decided, as
+    a dict -- alone, heavy, hi, crawl_rpw, crawl_grid (workgroups), crawl_ran, and records, the
+    count the device's last completed crawl pass reported (wait for the launch first).  Host
+    state only: no HIP call."""
+    raw = (ctypes.c_uint64 * 8)()
+    check(lib().vr_debug_last_launch(int(device), raw), "vr_debug_last_launch")
+    return dict(zip(LAST_LAUNCH, (int(x) for x in raw)))
+
+
 def render_tiles(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, lighting: _capi.VrLighting,
                  info: VoxelSceneInfo, width: int, height: int, band_rows: int, tile_cols: int, rank: int,
                  nranks: int, out: torch.Tensor, stream=None) -> torch.Tensor:
