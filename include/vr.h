@@ -56,7 +56,7 @@ typedef struct {
     int32_t use_shadows;
 } vr_lighting;
 
-/* Per-device scene (changed only by vr_scene_edit): region table + VCS or cuckoo storage images.
+/* Per-device scene (changed only by vr_scene_edit and vr_scene_paint): region table + VCS or cuckoo storage images.
  * Replaces VoxelSceneCPU::generateVoxelScene's device pointer table
  * (geometry/VoxelSceneCPU.cuh:49-93) plus the device-side virtual adapters
  * built by the generateVoxelScene kernel (renderer/Renderer.cuh:1066-1086). */
@@ -175,6 +175,66 @@ int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n
 int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capacity,
                     int outputs_on_device, void* stream, size_t* n_out);
 
+/* vr_scene_lookup's answer for a voxel that is not stored.  Equal to VR_VOXEL_REMOVE on purpose:
+ * vr_scene_edit(xyz, vr_scene_lookup(xyz)) changes nothing. */
+#define VR_VOXEL_ABSENT 0xFFFFFFFFu
+
+/* What is stored at (x, y, z): rgb[i] is the stored colour (< 2^24) of world voxel xyz[3i..3i+2]
+ * (the coordinates vr_scene_edit, vr_scene_voxels and vr_hit.voxel use), or VR_VOXEL_ABSENT.
+ * Set membership in the voxel set vr_scene_voxels returns -- e.g. whether a pick's
+ * voxel + normal really is empty, a collision probe, occupancy sampling -- and not the
+ * reference lookups' behaviour for coordinates outside a region: a world coordinate always has
+ * local coordinates in [0, 64).
+ *
+ * No voxel is rejected.  Any int32 coordinates, INT32_MIN and INT32_MAX included, whose 64^3
+ * region (floor(c / 64) per axis) lies outside the scene's frame give ABSENT, as do a null
+ * region, an absent cluster and an absent key.
+ *
+ * xyz: 3n int32, on the scene's device when inputs_on_device != 0; rgb: n words, on the device
+ * when outputs_on_device != 0.  Host arrays are staged through device buffers the call allocates
+ * and frees; with everything on the device it allocates nothing.  The work (one small kernel,
+ * one lane per query) runs on `stream` and the call returns when rgb[0..n) are written.
+ * n == 0 returns VR_OK and does nothing.  As a pick, a lookup is not a render launch: no ring
+ * slot, nothing learned or forgotten.
+ *
+ * VR_E_INVALID: s NULL; xyz or rgb NULL with n > 0; n >= 2^31; a stream that is capturing a HIP
+ * graph. */
+int vr_scene_lookup(const vr_scene* s, const int32_t* xyz, size_t n, int inputs_on_device,
+                    uint32_t* rgb, int outputs_on_device, void* stream);
+
+/* Recolour stored voxels in place, without the rebuild vr_scene_edit makes: edit i sets the
+ * colour of voxel xyz[3i..3i+2] to rgb[i] (< 2^24) if that voxel is stored; otherwise it does
+ * nothing and the voxel is counted in *n_absent (may be NULL).  A paint never inserts and never
+ * removes.  Later edits of a coordinate win over earlier ones, whatever the batch's size or
+ * order otherwise.  inputs_on_device != 0: xyz/rgb are buffers on the scene's device.
+ *
+ * Afterwards the five buffers of vr_scene_digest are byte for byte what vr_scene_edit gives for
+ * the same batch restricted to stored voxels, and what vr_scene_create gives for the recoloured
+ * voxel set; vr_scene_get_info is unchanged.  The cost is O(n) -- three small kernels and one
+ * 8-byte readback -- and nothing is sized by the scene; with the arrays on the device the call
+ * allocates nothing (the scene's first paint allocates 8 bytes that the scene keeps).
+ *
+ * Every check comes before any write.  VR_E_INVALID, with the scene untouched: s NULL; xyz or
+ * rgb NULL with n > 0; n >= 2^31; a colour >= 2^24 (the message names the first such index;
+ * VR_VOXEL_REMOVE is such a colour: to remove, use vr_scene_edit); a stream that is capturing a
+ * HIP graph.  n == 0 returns VR_OK and does nothing (*n_absent = 0).
+ * A HIP error after the writes have begun returns VR_E_HIP: the colours of the batch's voxels
+ * are then unspecified (every other voxel, and the scene's structure, are as they were).
+ *
+ * Ordering is vr_scene_edit's: the work runs on `stream` and the call returns when the colours
+ * are written.  Renders of this scene queued earlier on `stream` see the old colours.  The caller
+ * must have NO render of this scene in flight on another stream, and must not call
+ * vr_scene_edit, vr_scene_paint, vr_scene_voxels or vr_render* on this scene from another thread
+ * meanwhile.
+ *
+ * Unlike vr_scene_edit, a paint does not make the next render a first render: the scene's
+ * buffers are not replaced and its views keep their learned orders and crawl skips (vr_forget_orders
+ * is not implied).  That is sound because no walk reads a colour except to compare it with the
+ * empty marker, and the shadow walk starts whatever the lit colour is: a recolour changes
+ * neither which pixels defer to the crawl pass nor any walk's length. */
+int vr_scene_paint(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n,
+                   int inputs_on_device, void* stream, size_t* n_absent /* may be NULL */);
+
 /* vr_hit.status */
 #define VR_HIT_MISS    0u  /* the walk left the scene: the pixel is background */
 #define VR_HIT_VOXEL   1u  /* the walk read a stored voxel */
@@ -205,7 +265,7 @@ typedef struct {            /* 64 bytes, 16-byte aligned records */
  *   normal  the REFERENCE's normal, the one the lighting used (getNormalFromTValues,
  *           Renderer.cuh:237-247, or the axis step's): not always the geometric face the ray
  *           crossed.  voxel + normal is usually the empty neighbour to build on, but that
- *           is not guaranteed.
+ *           is not guaranteed (vr_scene_lookup tells).
  *   point   region-local.  The scene-space position is region * 64 + point; the lighting's
  *           world point is translation + region * 64 + point (unscaled, as the reference's).
  *

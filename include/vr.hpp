@@ -68,6 +68,7 @@ public:
     }
     ~DeviceScene() { vr_scene_destroy(s_); }
     const vr_scene* get() const { return s_; }
+    vr_scene* get() { return s_; }
     vr_scene_info info() const {
         vr_scene_info i{};
         check(vr_scene_get_info(s_, &i), "vr_scene_get_info");
@@ -156,6 +157,27 @@ inline std::vector<vr_hit> pick(uint32_t width, uint32_t height, RayMarchAlgorit
                   0, hits.data(), 0, stream),
           "pick");
     return hits;
+}
+
+// vr_scene_lookup: the stored colour of each world voxel xyz[3i..3i+2] (what pick()'s `voxel` and
+// vr_scene_edit use), or VR_VOXEL_ABSENT -- e.g. whether a pick's voxel + normal is free to build
+// on.  Host array in, host colours out; returns when they are written.
+inline std::vector<uint32_t> lookup(const DeviceScene& scene, const std::vector<int32_t>& xyz, void* stream = nullptr) {
+    if (xyz.size() % 3 != 0) throw Error(VR_E_INVALID, "lookup: xyz needs three coordinates per voxel");
+    std::vector<uint32_t> rgb(xyz.size() / 3);
+    check(vr_scene_lookup(scene.get(), xyz.data(), rgb.size(), 0, rgb.data(), 0, stream), "lookup");
+    return rgb;
+}
+
+// vr_scene_paint: recolour the stored voxels among xyz in place (later edits of a coordinate win);
+// returns how many of the edits named a voxel that is not stored (they do nothing).  The scene's
+// views keep their learned orders: a painter's loop is pick -> paint -> render.
+inline size_t paint(DeviceScene& scene, const std::vector<int32_t>& xyz, const std::vector<uint32_t>& rgb,
+                    void* stream = nullptr) {
+    if (xyz.size() != 3 * rgb.size()) throw Error(VR_E_INVALID, "paint: xyz and rgb lengths differ");
+    size_t absent = 0;
+    check(vr_scene_paint(scene.get(), xyz.data(), rgb.data(), rgb.size(), 0, stream, &absent), "paint");
+    return absent;
 }
 
 // vr_trace: the closest hit of each ray (any origin, any direction length), as vr_hit records --

@@ -9,7 +9,7 @@ CLI is bin/VoxelRaymarcher.
 """
 from ._capi import LIB_PATH, VrError, lib
 from .output import FrameWriter, ImageWriter, encode_png, write_png
-from .renderer import (CONFIGS, HIT_DTYPE, VOXEL_REMOVE, Build, HitStatus, Camera, DeviceScene, Kernel, Occupancy, PreparedRender, RayMarchAlgorithm,
+from .renderer import (CONFIGS, HIT_DTYPE, VOXEL_ABSENT, VOXEL_REMOVE, Build, HitStatus, Camera, DeviceScene, Kernel, Occupancy, PreparedRender, RayMarchAlgorithm,
                        RenderConfig,
                        Schedule, StorageType, VoxelSceneCPU, VoxelSceneInfo, assemble_tiles_device, band_buffer_words,
                        create_scene, deal_stride_default, debug_capture_lane_order, debug_force_in_flight, debug_lane_order, debug_last_launch,
@@ -19,7 +19,7 @@ from .renderer import (CONFIGS, HIT_DTYPE, VOXEL_REMOVE, Build, HitStatus, Camer
                        setup_constant_values, synth_scene, tile_buffer_words, write_binary_scene, write_voxel_file)
 
 __all__ = ["LIB_PATH", "VrError", "lib", "FrameWriter", "ImageWriter", "encode_png", "write_png", "CONFIGS", "HIT_DTYPE", "HitStatus",
-           "VOXEL_REMOVE", "Build", "pick", "RAY_DTYPE", "TraceOrder", "camera_rays", "shade", "trace",
+           "VOXEL_ABSENT", "VOXEL_REMOVE", "Build", "pick", "RAY_DTYPE", "TraceOrder", "camera_rays", "shade", "trace",
            "Camera", "DeviceScene", "Kernel", "Occupancy", "PreparedRender", "RayMarchAlgorithm", "RenderConfig", "Schedule",
            "StorageType", "VoxelSceneCPU", "VoxelSceneInfo", "assemble_tiles_device", "band_buffer_words",
            "create_scene", "deal_stride_default", "debug_capture_lane_order", "debug_force_in_flight", "debug_lane_order", "debug_last_launch",

@@ -102,6 +102,8 @@ SIGNATURES = {
     "vr_scene_destroy": (None, [c_void_p]),
     "vr_scene_edit": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "vr_scene_voxels": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_size_t)]),
+    "vr_scene_lookup": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "vr_scene_paint": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_size_t)]),
     "vr_render": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float), c_uint32,
                           c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
     "vr_render_bands": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float),

@@ -20,6 +20,13 @@
 //                                 the render would give it -- vr_shade, with the run's scale and
 //                                 lighting flags and a zero translation -- then the --trace text
 //                                 of its hit; not with --gpus N > 1)
+//                   [--lookup X,Y,Z]...  (after the shades: one line per query with the colour
+//                                 stored at world voxel (X, Y, Z), signed integers, or "absent"
+//                                 -- vr_scene_lookup; not with --gpus N > 1)
+//                   [--paint X,Y,Z,RRGGBB]...  (before the render, so output.png shows it: set
+//                                 the colour (hex) of stored voxel (X, Y, Z) -- vr_scene_paint, all
+//                                 of them as one batch in the order given; a voxel that is not
+//                                 stored gets a line on stderr; not with --gpus)
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -90,6 +97,30 @@ bool parse_pixel(const char* s, uint32_t& x, uint32_t& y) {
     return *s == 0;
 }
 
+// "X,Y,Z" -> three signed 32-bit decimals, then (colour != null) ",RRGGBB" -> a hex colour below
+// 2^32 (vr_scene_paint refuses one above 24 bits); false on malformed input.
+bool parse_voxel(const char* s, int32_t xyz[3], uint32_t* colour) {
+    char* end = nullptr;
+    for (int i = 0; i < 3; ++i) {
+        const long long v = std::strtoll(s, &end, 10);
+        if (end == s || v < INT32_MIN || v > INT32_MAX) return false;
+        xyz[i] = (int32_t)v;
+        s = end;
+        if (i < 2 || colour) {
+            if (*s != ',') return false;
+            ++s;
+        }
+    }
+    if (colour) {
+        if (*s == '-' || *s == '+' || *s == ' ') return false;
+        const unsigned long long v = std::strtoull(s, &end, 16);
+        if (end == s || v > 0xFFFFFFFFull) return false;
+        *colour = (uint32_t)v;
+        s = end;
+    }
+    return *s == 0;
+}
+
 bool is_integer(const char* s) {
     if (!s || !*s) return false;
     if (*s == '-' || *s == '+') ++s;
@@ -120,6 +151,9 @@ int main(int argc, char* argv[]) {
     std::vector<uint32_t> pick_x, pick_y;    // --pick X,Y (repeatable)
     std::vector<vr_ray> trace_rays;          // --trace OX,OY,OZ,DX,DY,DZ (repeatable)
     std::vector<vr_ray> shade_rays;          // --shade OX,OY,OZ,DX,DY,DZ (repeatable)
+    std::vector<int32_t> lookup_xyz;         // --lookup X,Y,Z (repeatable)
+    std::vector<int32_t> paint_xyz;          // --paint X,Y,Z,RRGGBB (repeatable)
+    std::vector<uint32_t> paint_rgb;
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -169,11 +203,30 @@ int main(int argc, char* argv[]) {
             }
             shade_rays.push_back(ray);
         }
+        else if (a == "--lookup") {
+            int32_t v[3];
+            if (!parse_voxel(next("--lookup"), v, nullptr)) {
+                std::cerr << "--lookup needs X,Y,Z (voxel coordinates)" << std::endl;
+                std::exit(2);
+            }
+            lookup_xyz.insert(lookup_xyz.end(), v, v + 3);
+        }
+        else if (a == "--paint") {
+            int32_t v[3];
+            uint32_t c = 0;
+            if (!parse_voxel(next("--paint"), v, &c)) {
+                std::cerr << "--paint needs X,Y,Z,RRGGBB (voxel coordinates and a hex colour)" << std::endl;
+                std::exit(2);
+            }
+            paint_xyz.insert(paint_xyz.end(), v, v + 3);
+            paint_rgb.push_back(c);
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
-                         "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]..." << std::endl;
+                         "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
+                         "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]..." << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -197,6 +250,14 @@ int main(int argc, char* argv[]) {
     }
     if (!shade_rays.empty() && multi && gpus > 1) {
         std::cerr << "ERROR: --shade is a single-GPU query: not with --gpus " << gpus << std::endl;
+        return 2;
+    }
+    if (!lookup_xyz.empty() && multi && gpus > 1) {
+        std::cerr << "ERROR: --lookup is a single-GPU query: not with --gpus " << gpus << std::endl;
+        return 2;
+    }
+    if (!paint_rgb.empty() && multi) {       // (every rank renders a replica of its own)
+        std::cerr << "ERROR: --paint changes this process's single-GPU scene: not with --gpus" << std::endl;
         return 2;
     }
     // argv[1] = scale (Main.cu:181-186); optional here (README.md:22-25 omits it).
@@ -254,6 +315,15 @@ int main(int argc, char* argv[]) {
         uint64_t slots = (uint64_t)info.diameter * info.diameter * info.diameter;
         std::cout << "There are : " << info.region_count << "/" << slots << " regions that are filled" << std::endl;
 
+        // --paint: recolour stored voxels before anything is rendered (vr_scene_paint, one batch)
+        if (!paint_rgb.empty() && vrx::paint(scene, paint_xyz, paint_rgb) != 0) {
+            const std::vector<uint32_t> stored = vrx::lookup(scene, paint_xyz);
+            for (size_t i = 0; i < stored.size(); ++i)
+                if (stored[i] == VR_VOXEL_ABSENT)
+                    std::cerr << "paint " << paint_xyz[3 * i] << " " << paint_xyz[3 * i + 1] << " " << paint_xyz[3 * i + 2]
+                              << " absent: nothing painted" << std::endl;
+        }
+
         float aspect = (float)width / (float)height;             // Main.cu:197
         vrx::Camera camera({6.0f, 2.0f, 6.0f}, {0.0f, 0.0f, -1.0f}, {0.0f, 1.0f, 0.0f}, 60.0f, aspect);
         vrx::VoxelSceneInfo sinfo({0.0f, 0.0f, 0.0f}, scale);
@@ -310,6 +380,17 @@ int main(int argc, char* argv[]) {
             }
             std::fflush(stdout);
         };
+        // --lookup: the colour stored at each given voxel (vr_scene_lookup), printed after the shades
+        auto print_lookups = [&]() {
+            if (lookup_xyz.empty()) return;
+            const std::vector<uint32_t> stored = vrx::lookup(scene, lookup_xyz);
+            for (size_t i = 0; i < stored.size(); ++i) {
+                std::printf("lookup %d %d %d ", lookup_xyz[3 * i], lookup_xyz[3 * i + 1], lookup_xyz[3 * i + 2]);
+                if (stored[i] == VR_VOXEL_ABSENT) std::printf("absent\n");
+                else std::printf("color 0x%06X\n", stored[i]);
+            }
+            std::fflush(stdout);
+        };
         if (multi) {
             // The frame image-tiled over devices 0..gpus-1, RCCL-gathered to device 0 (multi_gpu.h)
             vrx::MultiGpuFrame mg;
@@ -336,6 +417,7 @@ int main(int argc, char* argv[]) {
             print_picks();                   // (--gpus 1: the scene of this process's device)
             print_traces();
             print_shades();
+            print_lookups();
             std::vector<uint8_t> host;
             if (!mg.download(host)) {
                 std::cerr << "ERROR: " << mg.error() << std::endl;
@@ -371,6 +453,7 @@ int main(int argc, char* argv[]) {
         print_picks();
         print_traces();
         print_shades();
+        print_lookups();
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,
         // async copy into pinned memory, parallel PNG encode (vr_png_write).
         const size_t nbytes = (size_t)width * height * 3;

@@ -65,7 +65,8 @@ struct vr_scene {
     const uint64_t serial;
     explicit vr_scene(uint64_t id) : serial(id) {}
     // bumped by every successful non-empty vr_scene_edit: with `serial`, the identity of the
-    // scene's CONTENT (which pixels a view defers depends on it; vr_launch.cpp view_key)
+    // scene's CONTENT (which pixels a view defers depends on it; vr_launch.cpp view_key).
+    // vr_scene_paint does not bump it: a recolour changes no deferral and no walk length
     uint64_t revision = 0;
     int device = 0;
     vr_store store = VR_STORE_VCS;
@@ -76,6 +77,9 @@ struct vr_scene {
     vr::DevBuf region_slot, vcs_mask, vcs_vals, ht_meta, ht_slots;
     vr::DevBuf vcs_cbits;   // derived (not part of vr_scene_digest): cluster-existence bits per region
     vr::DevBuf ht_filter;   // derived (not part of vr_scene_digest): cuckoo key-presence bits per region
+    // vr_scene_paint's two result words on the device (vr_internal.h launch_paint_check): made by
+    // the scene's first paint, kept for the next ones, freed with the scene; no part of the image
+    uint32_t* paint_stat = nullptr;
     uint64_t device_bytes() const {
         return region_slot.bytes + vcs_mask.bytes + vcs_vals.bytes + ht_meta.bytes + ht_slots.bytes + vcs_cbits.bytes +
                ht_filter.bytes;

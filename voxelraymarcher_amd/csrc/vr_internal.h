@@ -1,5 +1,5 @@
 // vr_internal.h -- layouts shared by the host builder (vr_scene.cpp) and the
-// HIP kernels (vr_march.hip, vr_order.hip, vr_query.hip, vr_shade.hip, vr_util.hip; the walker: vr_walk.h).  See DESIGN.md "Data layout in HBM".
+// HIP kernels (vr_march.hip, vr_order.hip, vr_query.hip, vr_shade.hip, vr_util.hip, vr_access.hip; the walker: vr_walk.h).  See DESIGN.md "Data layout in HBM".
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,7 +41,7 @@ constexpr uint32_t kVcsMaxRegions = 65536u;
 // words of a cuckoo region's key-presence filter (64^3 bits)
 constexpr uint32_t kHashFilterWords = 8192u;
 
-// Device view of one scene (vr_scene_edit replaces its buffers as a set).  Offsets are 32-bit word indices.
+// Device view of one scene (vr_scene_edit replaces its buffers as a set; vr_scene_paint stores colours into them).  Offsets are 32-bit word indices.
 //  region_slot[D^3]          : region index r, or kNone (null StorageStructure*)
 //  VCS   : vcs_mask[r*8192 + slot*16 + w]  (one 128-B record per cluster of an
 //                              occupied region; VoxelClusterStore::deviceBlockMemAddress
@@ -213,6 +213,19 @@ hipError_t launch_camera_rays(const KView& v, const uint32_t* px, const uint32_t
 // already freed and null).
 hipError_t trace_order(const KScene& s, const KView& v, const void* rays, uint32_t n, hipStream_t stream,
                        void** scratch, const uint32_t** idx);
+// (vr_access.hip: voxel access by coordinate)
+// vr_scene_lookup's kernel: rgb[i] = the stored colour of world voxel xyz[3i..3i+2], or 0xFFFFFFFF
+// (VR_VOXEL_ABSENT) when it is not stored; one lane per query.
+hipError_t launch_lookup(int store, const KScene& s, const int32_t* xyz, uint32_t n, uint32_t* rgb, hipStream_t stream);
+// vr_scene_paint, before any write: sets stat[0] to the first index whose colour is >= 2^24
+// (0xFFFFFFFF: none) and stat[1] to 0xFFFFFFFF - the number of edits whose voxel is not stored.
+hipError_t launch_paint_check(int store, const KScene& s, const int32_t* xyz, const uint32_t* rgb, uint32_t n,
+                              uint32_t* stat, hipStream_t stream);
+// vr_scene_paint's writes into vcs_vals / the value halves of ht_slots: the tag kernel and the
+// resolve kernel (the last edit of a voxel wins).  n < 2^31, every colour < 2^24, and nothing else
+// may run on the scene between the two.
+hipError_t launch_paint_apply(int store, const KScene& s, const int32_t* xyz, const uint32_t* rgb, uint32_t n,
+                              hipStream_t stream);
 // (vr_util.hip, to launch_assemble_tiles)
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);

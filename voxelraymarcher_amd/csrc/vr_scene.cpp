@@ -1,5 +1,6 @@
 // vr_scene.cpp -- scene build (region bucketing, VCS and cuckoo images) on the host or
-// through the device builder, device upload, and the scene entry points of include/vr.h.
+// through the device builder, device upload, and the scene entry points of include/vr.h
+// (create, digest, edit, voxels, and access by coordinate: lookup and paint).
 //
 // Replaces, on the host: VoxelSceneCPU (geometry/VoxelSceneCPU.cuh:13-131) and
 // the VoxelClusterStore / CuckooHashTable constructors
@@ -103,6 +104,7 @@ void free_scene(vr_scene* s) {
                       &s->ht_filter};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    if (s->paint_stat) (void)hipFree(s->paint_stat);
     delete s;
 }
 
@@ -501,6 +503,84 @@ int vr_scene_edit(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n
     for (auto b : bufs) std::swap(s->*b, (*t).*b);
     ++s->revision;
     return VR_OK;   // t, now the old image, is freed here
+}
+
+// The colour stored at each coordinate (vr.h; kernel: vr_access.hip).  As the queries of
+// vr_query_api.cpp it is no render launch: nothing the render path keeps per device is touched.
+int vr_scene_lookup(const vr_scene* s, const int32_t* xyz, size_t n, int inputs_on_device, uint32_t* rgb,
+                    int outputs_on_device, void* stream) {
+    static_assert(VR_VOXEL_ABSENT == VR_VOXEL_REMOVE, "vr_scene_edit(xyz, vr_scene_lookup(xyz)) changes nothing");
+    if (!s) return fail(VR_E_INVALID, "vr_scene_lookup: scene is NULL");
+    if (n && (!xyz || !rgb)) return fail(VR_E_INVALID, "vr_scene_lookup: xyz/rgb NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_scene_lookup: too many queries");
+    if (n == 0) return VR_OK;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_scene_lookup")) return rc;
+    Staging sg(st);
+    const int32_t* dxyz = inputs_on_device ? xyz : (const int32_t*)sg.upload(xyz, 3 * n * sizeof(int32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_scene_lookup: query upload");
+    uint32_t* drgb = outputs_on_device ? rgb : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_scene_lookup: colour buffer");
+    hipError_t e = vr::launch_lookup((int)s->store, vr::kscene(s), dxyz, (uint32_t)n, drgb, st);
+    if (e == hipSuccess && drgb != rgb) {
+        sg.fetch(rgb, drgb, n * sizeof(uint32_t));
+        e = sg.err;
+    }
+    const hipError_t es = sg.sync();
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "vr_scene_lookup");
+    return VR_OK;
+}
+
+// Recolour stored voxels in place (vr.h; kernels: vr_access.hip).  One store per voxel into the
+// live image: no buffer is replaced and the revision stays, so the views' learned orders and
+// crawl skips stay bound -- no walk reads a colour except to compare it with kEmpty, so a
+// recolour moves no deferral and no walk length.
+int vr_scene_paint(vr_scene* s, const int32_t* xyz, const uint32_t* rgb, size_t n, int inputs_on_device, void* stream,
+                   size_t* n_absent) {
+    if (!s) return fail(VR_E_INVALID, "vr_scene_paint: scene is NULL");
+    if (n && (!xyz || !rgb)) return fail(VR_E_INVALID, "vr_scene_paint: xyz/rgb NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_scene_paint: too many edits");
+    if (n_absent) *n_absent = 0;
+    if (n == 0) return VR_OK;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_scene_paint")) return rc;
+    if (!s->paint_stat) {
+        const hipError_t e = hipMalloc((void**)&s->paint_stat, 2 * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            s->paint_stat = nullptr;
+            return hip_fail(e, "vr_scene_paint: hipMalloc");
+        }
+    }
+    Staging sg(st);
+    const int32_t* dxyz = xyz;
+    const uint32_t* drgb = rgb;
+    if (!inputs_on_device) dxyz = voxels_on_device(sg, xyz, rgb, n, drgb);
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_scene_paint: edit upload");
+    const vr::KScene k = vr::kscene(s);
+    // every check before any write: the first colour that is no colour, and the absent count
+    uint32_t stat[2] = {0u, 0u};
+    hipError_t e = vr::launch_paint_check((int)s->store, k, dxyz, drgb, (uint32_t)n, s->paint_stat, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stat, s->paint_stat, sizeof stat, hipMemcpyDeviceToHost, st);
+    hipError_t es = sg.sync();
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "vr_scene_paint: check");
+    if (stat[0] != 0xFFFFFFFFu) {
+        uint32_t c = 0;
+        if (!inputs_on_device) c = rgb[stat[0]];
+        else if ((e = hipMemcpy(&c, rgb + stat[0], sizeof c, hipMemcpyDeviceToHost)) != hipSuccess)
+            return hip_fail(e, "vr_scene_paint: check");
+        return fail(VR_E_INVALID, "vr_scene_paint: voxel colour " + std::to_string(c) + " at index " +
+                                      std::to_string(stat[0]) + " exceeds 24-bit RGB (a paint never removes)");
+    }
+    e = vr::launch_paint_apply((int)s->store, k, dxyz, drgb, (uint32_t)n, st);
+    es = sg.sync();      // (whatever e is: the tag kernel may be queued on the staged arrays)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "vr_scene_paint (the colours of the batch's voxels are unspecified)");
+    if (n_absent) *n_absent = (size_t)(0xFFFFFFFFu - stat[1]);
+    return VR_OK;
 }
 
 int vr_scene_voxels(const vr_scene* s, int32_t* xyz, uint32_t* rgb, size_t capacity, int outputs_on_device, void* stream,

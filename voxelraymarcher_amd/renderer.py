@@ -92,6 +92,26 @@ class VoxelSceneInfo:
 
 
 VOXEL_REMOVE = 0xFFFFFFFF   # VR_VOXEL_REMOVE: as an edit's colour, delete the voxel
+VOXEL_ABSENT = 0xFFFFFFFF   # VR_VOXEL_ABSENT: a lookup's answer for a voxel that is not stored
+
+
+def _voxel_batch(xyz, rgb):
+    """The (xyz, rgb) batch of edit() and paint() as (int32 [n,3], 32-bit [n], on_device):
+    contiguous CUDA tensors when xyz is one, numpy arrays otherwise."""
+    if hasattr(xyz, "is_cuda") and xyz.is_cuda:
+        xyz = xyz.to(torch.int32).contiguous().reshape(-1, 3)
+        rgb = rgb.contiguous().reshape(-1)
+        if rgb.dtype not in (torch.int32, torch.uint32):
+            # (VOXEL_REMOVE does not fit int32: wrap int64 colours to 32 bits)
+            rgb = ((((rgb.to(torch.int64) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)).contiguous()
+        dev = 1
+    else:
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint32).reshape(-1)
+        dev = 0
+    if xyz.shape[0] != rgb.shape[0]:
+        raise ValueError("xyz and rgb lengths differ")
+    return xyz, rgb, dev
 
 
 class DeviceScene:
@@ -127,23 +147,41 @@ class DeviceScene:
         and returns when the scene is ready.  With several GPUs every rank holds its own
         scene: the same batch applied on every rank gives identical images."""
         sp = _stream_ptr(stream)
-        if hasattr(xyz, "is_cuda") and xyz.is_cuda:
+        xyz, rgb, dev = _voxel_batch(xyz, rgb)
+        check(lib().vr_scene_edit(self.handle, _ptr(xyz), _ptr(rgb), rgb.shape[0], dev, sp), "vr_scene_edit")
+
+    def lookup(self, xyz, stream=None):
+        """vr_scene_lookup: the stored colour of each world voxel xyz[i], or VOXEL_ABSENT -- for
+        any int32 coordinates, inside the scene's frame or not.  A numpy array (or list) gives
+        numpy uint32[n]; a CUDA tensor on the scene's device gives an int32 tensor there with
+        the same words (VOXEL_ABSENT reads as -1).  Runs on `stream` (default: the current
+        stream) and returns when the colours are written; no render launch."""
+        dev = int(hasattr(xyz, "is_cuda") and xyz.is_cuda)
+        if dev:
             xyz = xyz.to(torch.int32).contiguous().reshape(-1, 3)
-            rgb = rgb.contiguous().reshape(-1)
-            if rgb.dtype not in (torch.int32, torch.uint32):
-                # (VOXEL_REMOVE does not fit int32: wrap int64 colours to 32 bits)
-                rgb = ((((rgb.to(torch.int64) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)).contiguous()
-            if xyz.shape[0] != rgb.shape[0]:
-                raise ValueError("xyz and rgb lengths differ")
-            check(lib().vr_scene_edit(self.handle, c_void_p(xyz.data_ptr()), c_void_p(rgb.data_ptr()), rgb.shape[0], 1,
-                                      sp), "vr_scene_edit")
-            return
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
-        rgb = np.ascontiguousarray(rgb, dtype=np.uint32).reshape(-1)
-        if xyz.shape[0] != rgb.shape[0]:
-            raise ValueError("xyz and rgb lengths differ")
-        check(lib().vr_scene_edit(self.handle, xyz.ctypes.data_as(c_void_p), rgb.ctypes.data_as(c_void_p),
-                                  rgb.shape[0], 0, sp), "vr_scene_edit")
+            rgb = torch.empty(xyz.shape[0], dtype=torch.int32, device=xyz.device)
+        else:
+            xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
+            rgb = np.zeros(xyz.shape[0], dtype=np.uint32)
+        if xyz.shape[0]:
+            check(lib().vr_scene_lookup(self.handle, _ptr(xyz), xyz.shape[0], dev, _ptr(rgb), dev, _stream_ptr(stream)),
+                  "vr_scene_lookup")
+        return rgb
+
+    def paint(self, xyz, rgb, stream=None) -> int:
+        """vr_scene_paint: recolour stored voxels in place.  Edit i sets voxel xyz[i] to colour
+        rgb[i] (< 2^24) if it is stored; later edits of a coordinate win.  Returns the number of
+        edits whose voxel is not stored (they do nothing: a paint never inserts or removes).
+        xyz/rgb as for edit().  A colour >= 2^24 raises VrError and leaves the scene as it was.
+        O(n), no rebuild, and -- unlike edit() -- the scene's views keep what the renderer has
+        learned about them.  Runs on `stream` (default: the current stream) and returns when the
+        colours are written."""
+        sp = _stream_ptr(stream)
+        xyz, rgb, dev = _voxel_batch(xyz, rgb)
+        absent = c_size_t(0)
+        check(lib().vr_scene_paint(self.handle, _ptr(xyz), _ptr(rgb), rgb.shape[0], dev, sp, ctypes.byref(absent)),
+              "vr_scene_paint")
+        return int(absent.value)
 
     def voxels(self, device: bool = False, stream=None):
         """vr_scene_voxels: the scene's voxels, (xyz int32[n,3], rgb uint32[n]) as numpy arrays,
