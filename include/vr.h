@@ -377,6 +377,59 @@ int vr_shade(const vr_scene* s, vr_algo algo, const vr_lighting* lit,
              uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
              uint32_t order, void* stream);
 
+/* vr_shade under several lights and an ambient term, from ONE primary walk per ray: L calls of
+ * vr_shade walk every primary ray L times; this walks it once and runs one lighting-and-shadow
+ * pass per light over the hits.
+ *
+ * Terms.  For ray i and light k, T_k(i) is the word vr_shade writes for rays[i] under lights[k]
+ * -- a plain vr_lighting, taken as data exactly as vr_shade takes it: applyLighting at the
+ * primary hit, times !shadow when lights[k].use_shadows, the shadow walk along that light's
+ * light_dir from the hit's point in the hit's region.  T_k(i) is 0 for a miss, 0 for a primary
+ * walk that never ends, and 0 for a shadow walk of light k that never ends (the other lights'
+ * terms still count).  Each light keeps every quirk of the reference: a point light's shadow
+ * walk still follows light_dir (Renderer.cuh:174-235).
+ * The ambient term T_a(i) exists when ambient != NULL: at a primary VOXEL hit with stored colour
+ * col, each channel c of col gives f2u((div255(c) * ambient[ch]) * 255.0f) -- the directional
+ * formula of applyLighting with the diffuse factor 1.0f and the light's colour replaced by
+ * ambient, the same fp32 operations in the same order, no contraction (f2u: NaN and negatives
+ * give 0) -- packed R << 16 | G << 8 | B.  It is 0 for a miss or a primary walk that never ends,
+ * and it has no shadow walk.
+ *
+ * Sum.  colors[i] = min(255, sum R) << 16 | min(255, sum G) << 8 | min(255, sum B) over every
+ * term, with R(w) = (w >> 16) & 0xFF, G(w) = (w >> 8) & 0xFF, B(w) = w & 0xFF.  Bits 24-31 of a
+ * term are dropped: they are non-zero only where light_color or an un-normalised light_dir pushes
+ * a channel past 255, which bleeds in the reference's packing.  The sums are of integers, so
+ * colors[i] does not depend on the order of the lights.  Hence: with n_lights == 1 and no ambient,
+ * colors[i] is vr_shade's word whenever that word is below 2^24; with n_lights == 0, colors[i]
+ * is the ambient term alone (bits 24-31 dropped), and 0 without ambient.
+ *
+ * hits (may be NULL): when given, hits[i] is byte for byte vr_shade's and vr_trace's record for
+ * rays[i]; status VR_HIT_NEVER is for a primary walk only.  The colours are the same words with
+ * and without it.  order is a vr_trace_order with vr_trace's meaning: the execution order only,
+ * never a word or a record; AUTO is GIVEN.  No ray and no lighting value is rejected.
+ *
+ * lights (n_lights blocks, at most VR_MAX_LIGHTS) and ambient (three floats, or NULL) are host
+ * arrays, read before the call returns.  rays, colors and hits are vr_shade's: n records on the
+ * scene's device (rays and hits 16-byte, colors 4-byte aligned) when the flag says so, host
+ * arrays staged through device buffers otherwise.  The call also allocates its per-ray hit
+ * state (32 bytes per ray) on the scene's device and frees it before it returns, on every
+ * path; a failure there is VR_E_NOMEM or VR_E_HIP.  The work runs on `stream` -- one primary
+ * kernel and one kernel per light -- and the call returns when the outputs are written.
+ * n == 0 returns VR_OK and does nothing.  Not a render launch: no ring slot, nothing learned or
+ * forgotten.
+ *
+ * VR_E_INVALID (nothing is written): s or translation NULL; lights NULL with n_lights > 0;
+ * n_lights > VR_MAX_LIGHTS; rays or colors NULL with n > 0; n >= 2^31; an unknown algorithm; an
+ * unknown order; a misaligned device array; a stream that is capturing a HIP graph. */
+#define VR_MAX_LIGHTS 64u
+int vr_shade_lights(const vr_scene* s, vr_algo algo,
+                    const vr_lighting* lights, size_t n_lights,
+                    const float ambient[3] /* may be NULL */,
+                    const float translation[3], uint32_t scale,
+                    const vr_ray* rays, size_t n, int inputs_on_device,
+                    uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
+                    uint32_t order, void* stream);
+
 /* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
  * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
  * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the

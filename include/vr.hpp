@@ -211,6 +211,24 @@ inline std::vector<uint32_t> shade(RayMarchAlgorithm algo, const VoxelSceneInfo&
     return colors;
 }
 
+// vr_shade_lights: shade() under several lights (at most VR_MAX_LIGHTS) and an optional ambient
+// term (three floats, or nullptr), from one primary walk per ray: the lights' words and the
+// ambient term summed per channel with a clamp at 255.  hits as for shade().  Host arrays in, host
+// arrays out; returns when they are written.
+inline std::vector<uint32_t> shadeLights(RayMarchAlgorithm algo, const VoxelSceneInfo& info,
+                                         const std::vector<vr_lighting>& lights, const float* ambient,
+                                         const DeviceScene& scene, const std::vector<vr_ray>& rays,
+                                         std::vector<vr_hit>* hits = nullptr, vr_trace_order order = VR_TRACE_ORDER_AUTO,
+                                         void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> colors(rays.size());
+    if (hits) hits->assign(rays.size(), vr_hit{});
+    check(vr_shade_lights(scene.get(), (vr_algo)algo, lights.data(), lights.size(), ambient, t, info.scale, rays.data(),
+                          rays.size(), 0, colors.data(), hits ? hits->data() : nullptr, 0, (uint32_t)order, stream),
+          "shadeLights");
+    return colors;
+}
+
 // vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
 // frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
 inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,

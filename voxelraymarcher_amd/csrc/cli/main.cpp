@@ -27,6 +27,13 @@
 //                                 the colour (hex) of stored voxel (X, Y, Z) -- vr_scene_paint, all
 //                                 of them as one batch in the order given; a voxel that is not
 //                                 stored gets a line on stderr; not with --gpus)
+//                   [--add-light DX,DY,DZ,R,G,B]...  (one more directional light of colour R,G,B, its
+//                                 direction normalised as --light-dir's, its shadows following
+//                                 --no-shadows) [--ambient R,G,B]  (an ambient term): with either,
+//                                 output.png is the vr_shade_lights frame -- the run's own light
+//                                 first, then the added ones, the terms summed per channel with a
+//                                 clamp at 255 -- and a line "lights <N> ambient <r> <g> <b>" is
+//                                 printed before "Wrote"; not with --gpus
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -154,6 +161,9 @@ int main(int argc, char* argv[]) {
     std::vector<int32_t> lookup_xyz;         // --lookup X,Y,Z (repeatable)
     std::vector<int32_t> paint_xyz;          // --paint X,Y,Z,RRGGBB (repeatable)
     std::vector<uint32_t> paint_rgb;
+    std::vector<vr_ray> added_lights;        // --add-light DX,DY,DZ,R,G,B (repeatable): direction, colour
+    bool has_ambient = false;                // --ambient R,G,B
+    float ambient[3] = {0.0f, 0.0f, 0.0f};
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -221,12 +231,28 @@ int main(int argc, char* argv[]) {
             paint_xyz.insert(paint_xyz.end(), v, v + 3);
             paint_rgb.push_back(c);
         }
+        else if (a == "--add-light") {
+            vr_ray l;                        // (six floats: the direction in `origin`, the colour in `direction`)
+            if (!parse_ray(next("--add-light"), l)) {
+                std::cerr << "--add-light needs DX,DY,DZ,R,G,B (a direction and a colour)" << std::endl;
+                std::exit(2);
+            }
+            added_lights.push_back(l);
+        }
+        else if (a == "--ambient") {
+            if (!parse_vec3(next("--ambient"), ambient)) {
+                std::cerr << "--ambient needs R,G,B" << std::endl;
+                std::exit(2);
+            }
+            has_ambient = true;
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
                          "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
-                         "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]..." << std::endl;
+                         "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]... [--add-light DX,DY,DZ,R,G,B]... "
+                         "[--ambient R,G,B]" << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -258,6 +284,15 @@ int main(int argc, char* argv[]) {
     }
     if (!paint_rgb.empty() && multi) {       // (every rank renders a replica of its own)
         std::cerr << "ERROR: --paint changes this process's single-GPU scene: not with --gpus" << std::endl;
+        return 2;
+    }
+    const bool lights_frame = !added_lights.empty() || has_ambient;
+    if (lights_frame && multi) {             // (the frame is one device's vr_shade_lights call)
+        std::cerr << "ERROR: --add-light and --ambient shade a single-GPU frame: not with --gpus" << std::endl;
+        return 2;
+    }
+    if (added_lights.size() + 1u > VR_MAX_LIGHTS) {
+        std::cerr << "ERROR: --add-light: at most " << (VR_MAX_LIGHTS - 1u) << " added lights" << std::endl;
         return 2;
     }
     // argv[1] = scale (Main.cu:181-186); optional here (README.md:22-25 omits it).
@@ -454,6 +489,45 @@ int main(int argc, char* argv[]) {
         print_traces();
         print_shades();
         print_lookups();
+        // --add-light / --ambient: the frame written is the vr_shade_lights one -- the camera rays
+        // of every pixel in 8x8-tile order (the order in which a frame's rays walk fastest), the
+        // run's own light first and then the added ones, the words scattered back to their pixels
+        if (lights_frame) {
+            std::vector<vr_lighting> lights(1, lit);
+            for (const vr_ray& l : added_lights) {
+                vr_lighting k = vrx::defaultLighting();
+                vrx::setLightDirection(k, l.origin[0], l.origin[1], l.origin[2]);
+                for (int i = 0; i < 3; ++i) k.light_color[i] = l.direction[i];
+                k.use_shadows = shadows;
+                lights.push_back(k);
+            }
+            const size_t n = (size_t)width * height;
+            std::vector<uint32_t> px, py;
+            px.reserve(n);
+            py.reserve(n);
+            for (uint32_t ty = 0; ty < height; ty += 8)
+                for (uint32_t tx = 0; tx < width; tx += 8)
+                    for (uint32_t y = ty; y < std::min(ty + 8u, height); ++y)
+                        for (uint32_t x = tx; x < std::min(tx + 8u, width); ++x) {
+                            px.push_back(x);
+                            py.push_back(y);
+                        }
+            vr_ray* rays = nullptr;
+            HIP_OK(hipMalloc(&rays, n * sizeof(vr_ray)));
+            const float t[3] = {sinfo.translationVector.x, sinfo.translationVector.y, sinfo.translationVector.z};
+            std::vector<uint32_t> words(n), frame(n);
+            int rc = vr_camera_rays(device, &camera.raw(), width, height, px.data(), py.data(), n, 0, rays, 1, nullptr);
+            if (rc == VR_OK)
+                rc = vr_shade_lights(scene.get(), (vr_algo)algo, lights.data(), lights.size(), has_ambient ? ambient : nullptr,
+                                     t, sinfo.scale, rays, n, 1, words.data(), nullptr, 0, VR_TRACE_ORDER_AUTO, nullptr);
+            (void)hipFree(rays);
+            vrx::check(rc, "lights frame");
+            for (size_t i = 0; i < n; ++i) frame[(size_t)py[i] * width + px[i]] = words[i];
+            HIP_OK(hipMemcpy(fb, frame.data(), n * 4, hipMemcpyHostToDevice));
+            std::printf("lights %zu ambient %.9g %.9g %.9g\n", lights.size(), has_ambient ? ambient[0] : 0.0f,
+                        has_ambient ? ambient[1] : 0.0f, has_ambient ? ambient[2] : 0.0f);
+            std::fflush(stdout);
+        }
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,
         // async copy into pinned memory, parallel PNG encode (vr_png_write).
         const size_t nbytes = (size_t)width * height * 3;

@@ -202,6 +202,18 @@ hipError_t launch_trace(int store, int algo, const KScene& s, const KView& v, co
 // too, from the same walk.  Of the view the lighting block, translation and scale_f are read.
 hipError_t launch_shade(int store, int algo, const KScene& s, const KView& v, const void* rays, const uint32_t* idx,
                         uint32_t n, uint32_t* colors, void* hits, hipStream_t stream);
+// vr_shade_lights' kernels (vr_lights.hip).  launch_lights_primary: the primary walk of each of n
+// rays (vr_ray records and idx as for launch_trace); state (32 bytes per ray, 16-byte aligned)
+// receives what a light pass needs of the hit, colors[r] the ambient term (ambient: three host
+// floats, or null: 0), hits (or null) launch_trace's records.  Of the view translation and
+// scale_f are read.  launch_light_term: one light's term for every ray with a hit -- the word
+// launch_shade writes under the view's lighting block -- summed into colors byte-wise with a
+// clamp at 255 per channel; after launch_lights_primary on the same stream, once per light.
+hipError_t launch_lights_primary(int store, int algo, const KScene& s, const KView& v, const void* rays,
+                                 const uint32_t* idx, uint32_t n, const float* ambient, void* state, uint32_t* colors,
+                                 void* hits, hipStream_t stream);
+hipError_t launch_light_term(int store, int algo, const KScene& s, const KView& v, const uint32_t* idx, uint32_t n,
+                             const void* state, uint32_t* colors, hipStream_t stream);
 // vr_camera_rays' kernel: the rays of pixels (px[i], py[i]) of the view's frame (one band over it).
 hipError_t launch_camera_rays(const KView& v, const uint32_t* px, const uint32_t* py, uint32_t n, void* rays,
                               hipStream_t stream);

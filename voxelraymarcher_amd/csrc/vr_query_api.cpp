@@ -1,5 +1,6 @@
-// vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace, vr_shade and
-// vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip, vr_shade.hip).  None is a render launch: no slot
+// vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace, vr_shade,
+// vr_shade_lights and vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip, vr_shade.hip,
+// vr_lights.hip).  None is a render launch: no slot
 // lease, no view key, nothing the render path keeps per device (vr_launch.cpp) is touched.  Each
 // takes its arrays on the host or on the device (vr_staging.h), and in each every argument
 // check comes before any device work.
@@ -182,6 +183,70 @@ int vr_shade(const vr_scene* s, vr_algo algo, const vr_lighting* lit, const floa
         e = sg.err;
     }
     return finish(sg, e, colors, dc, n * sizeof(uint32_t), "vr_shade");
+}
+
+// vr_shade's colours under several lights and an ambient term, from one primary walk (vr.h).
+int vr_shade_lights(const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights, const float ambient[3],
+                    const float translation[3], uint32_t scale, const vr_ray* rays, size_t n, int inputs_on_device,
+                    uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream) {
+    if (!s) return fail(VR_E_INVALID, "vr_shade_lights: scene is NULL");
+    if (!translation) return fail(VR_E_INVALID, "vr_shade_lights: translation NULL");
+    if (n_lights && !lights) return fail(VR_E_INVALID, "vr_shade_lights: lights NULL");
+    if (n_lights > VR_MAX_LIGHTS) return fail(VR_E_INVALID, "vr_shade_lights: too many lights (VR_MAX_LIGHTS)");
+    if (n && (!rays || !colors)) return fail(VR_E_INVALID, "vr_shade_lights: rays/colors NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_shade_lights: too many rays");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS)
+        return fail(VR_E_INVALID, "vr_shade_lights: unknown algorithm");
+    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
+        return fail(VR_E_INVALID, "vr_shade_lights: unknown order");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_shade_lights: device rays must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)colors & 3u) != 0u)
+        return fail(VR_E_INVALID, "vr_shade_lights: device colors must be 4-byte aligned");
+    if (outputs_on_device && hits && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_shade_lights: device hits must be 16-byte aligned");
+    // the trace's view for the primary walk (no camera, no light, no frame)
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
+    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
+    // AUTO is GIVEN, as vr_trace's (vr.h)
+    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_shade_lights")) return rc;
+    Staging sg(st);           // (owns every buffer below: freed on every path, after the stream has drained)
+    const void* dr = inputs_on_device ? rays : sg.upload(rays, n * sizeof(vr_ray));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: ray upload");
+    uint32_t* dc = outputs_on_device ? colors : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    void* dh = (outputs_on_device || !hits) ? hits : sg.make(n * sizeof(vr_hit));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: output buffers");
+    // the per-ray hit state between the primary pass and the light passes (32 bytes per ray)
+    void* state = sg.make(n * 32u);
+    if (sg.err == hipErrorOutOfMemory) return fail(VR_E_NOMEM, "vr_shade_lights: hit state: " + std::string(hipGetErrorString(sg.err)));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: hit state");
+    hipError_t e = hipSuccess;
+    const uint32_t* idx = nullptr;
+    if (coherent) {
+        void* scratch = nullptr;
+        e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &scratch, &idx);
+        sg.adopt(scratch);
+    }
+    if (e == hipSuccess)
+        e = vr::launch_lights_primary((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, ambient, state, dc,
+                                      dh, st);
+    for (size_t k = 0; k < n_lights && e == hipSuccess; ++k) {
+        // light k as vr_shade takes it: the render's lighting block in the same view
+        vr::KView lv = v;
+        vr::view_lighting(lv, &lights[k]);
+        e = vr::launch_light_term((int)s->store, (int)algo, vr::kscene(s), lv, idx, (uint32_t)n, state, dc, st);
+    }
+    if (e == hipSuccess && hits != dh) {        // (the records' way back; the colours': finish)
+        sg.fetch(hits, dh, n * sizeof(vr_hit));
+        e = sg.err;
+    }
+    return finish(sg, e, colors, dc, n * sizeof(uint32_t), "vr_shade_lights");
 }
 
 // The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.
