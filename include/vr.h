@@ -611,6 +611,39 @@ int vr_debug_skip_next_crawl(int device);
 int vr_debug_capture_lane_order(int device);
 int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t pcost_words, uint8_t* perm,
                         uint64_t perm_bytes);
+/* Test hook: the work order of the captured launch (vr_debug_capture_lane_order).  When that
+ * launch made its work order from the costs perm_kernel wrote under the new lane order, the
+ * capture -- taken after the work order's kernel -- also keeps both: cost (or NULL) takes
+ * 2 * info[2] * info[3] words, (tile-group row * info[2] + column) * 2 + wave, each
+ * max(primary) + max(shadow) walk length over the wave's 64 pixels (a cut block's: over the 8x8
+ * tile); order (or NULL) takes info[2] * info[3] words, (row << 16 | column) of the tile group
+ * the tile pass's i-th workgroup renders, heaviest first.  info is vr_debug_lane_order's; call
+ * with both NULL to ask whether a work order was captured.  VR_E_INVALID when none was (nothing
+ * captured, or the launch made no work order from those costs), for a word count that is not
+ * the captured one, or a device outside 0..63.  Host state only.  Never needed by a renderer. */
+int vr_debug_work_order(int device, uint32_t* cost, uint64_t cost_words, uint32_t* order, uint64_t order_words);
+/* Test hooks that run the two order kernels on the caller's input, in scratch device buffers
+ * of their own, on the null stream: no slot of the device's ring, nothing learned and no
+ * counter of vr_debug_order_uses is touched.  Each output buffer is followed by 256 guard bytes
+ * of the hook's own; VR_E_HIP if the kernel changed one (it wrote past its output).  Never
+ * needed by a renderer.
+ * vr_debug_lane_order_from: the lane order and the waves' costs of a frame of LW x rows pixels
+ * whose walk lengths are pcost_host (LW * rows words, row-major, primary << 16 | shadow).  info
+ * is filled as by vr_debug_lane_order; perm takes the order (perm_bytes: blocks * width * height
+ * * info[6]), cost 2 * info[2] * info[3] words, both laid out as vr_debug_lane_order and
+ * vr_debug_work_order return them.  Both are filled with 0xFF bytes before the kernel runs, so
+ * what it leaves unwritten shows (the perm entries of blocks cut by the frame's edge).  With
+ * pcost_host, perm and cost all NULL only info is filled (the sizes) and nothing runs.
+ * VR_E_INVALID for a NULL info, one of the three NULL, LW or rows outside 1..65536, a wrong
+ * perm_bytes or cost_words, or a device outside 0..63 -- all checked before any device work.
+ * vr_debug_work_order_from: the work order of a grid of `groups` tile groups in rows of
+ * `columns`, from cost_host (2 * groups words, the two waves' costs per group); order takes
+ * `groups` words, filled with 0xFF bytes before the kernel runs.  VR_E_INVALID for a NULL
+ * pointer, columns outside 1..4096, groups that is 0 or no multiple of columns, more than 8192
+ * rows, or a device outside 0..63 -- checked before any device work. */
+int vr_debug_lane_order_from(int device, const uint32_t* pcost_host, uint32_t LW, uint32_t rows, uint32_t info[8],
+                             uint8_t* perm, uint64_t perm_bytes, uint32_t* cost, uint64_t cost_words);
+int vr_debug_work_order_from(int device, const uint32_t* cost_host, uint32_t columns, uint32_t groups, uint32_t* order);
 /* Test hook: whether the device's launches rendered under learned orders.  Host counters kept
  * by the render launch, monotonic for the life of the process (vr_forget_orders does not reset
  * them); vr_pick moves none.  out[0] render launches that reached the tile pass, [1] lane

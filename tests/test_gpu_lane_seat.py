@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import oracle
+from tests.order_model import morton
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +21,6 @@ vr = pytest.importorskip("voxelraymarcher_amd")
 
 FRAMES = [(32, 32), (48, 40), (64, 32)]
 LAUNCHES = 40          # past two uses of each of the ring's 16 slots: every slot learns and reuses
-
-
-def morton(px, py):
-    """Bit 2i = bit i of the column, bit 2i + 1 = bit i of the row (low four bits of each);
-    a fifth column bit is bit 8, a fifth row bit bit 9."""
-    def spread4(v):
-        v = (v | v << 2) & 0x33
-        return (v | v << 1) & 0x55
-    return spread4(px & 15) | spread4(py & 15) << 1 | (px >> 4) << 8 | (py >> 4) << 9
 
 
 @pytest.mark.parametrize("size", FRAMES, ids=lambda s: f"{s[0]}x{s[1]}")

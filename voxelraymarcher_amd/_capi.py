@@ -120,6 +120,10 @@ SIGNATURES = {
     "vr_debug_skip_next_crawl": (c_int, [c_int]),
     "vr_debug_capture_lane_order": (c_int, [c_int]),
     "vr_debug_lane_order": (c_int, [c_int, POINTER(c_uint32), c_void_p, c_uint64, c_void_p, c_uint64]),
+    "vr_debug_work_order": (c_int, [c_int, c_void_p, c_uint64, c_void_p, c_uint64]),
+    "vr_debug_lane_order_from": (c_int, [c_int, c_void_p, c_uint32, c_uint32, POINTER(c_uint32), c_void_p, c_uint64,
+                                         c_void_p, c_uint64]),
+    "vr_debug_work_order_from": (c_int, [c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
     "vr_debug_order_uses": (c_int, [c_int, POINTER(c_uint64)]),
     "vr_debug_force_in_flight": (c_int, [c_int, c_int]),
     "vr_debug_last_launch": (c_int, [c_int, POINTER(c_uint64)]),

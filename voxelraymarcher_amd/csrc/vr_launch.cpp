@@ -164,12 +164,15 @@ struct SlotRing {
         // order bound, work orders made, launches with a work order bound, crawl passes skipped
         uint64_t uses[6] = {0, 0, 0, 0, 0, 0};
         // vr_debug_capture_lane_order (tests): the next lane order made on the device is kept
-        // here with the walk lengths it was made from, for vr_debug_lane_order
+        // here with the walk lengths it was made from, for vr_debug_lane_order; with it the
+        // waves' costs perm_kernel wrote and the work order that launch made from them, for
+        // vr_debug_work_order (empty when the launch made no work order from those costs)
         bool capture_lane = false;
         struct LaneCapture {
             uint32_t LW = 0, rows = 0, gx = 0, gy = 0;
             std::vector<uint32_t> pcost;
             std::vector<uint8_t> perm;
+            std::vector<uint32_t> cost, order;
         } lane_capture;
         // No other stream's launch is running on the device.  (The lock orders launches:
         // "previous" is well defined.  The event is queried only when there is a previous
@@ -368,25 +371,6 @@ hipError_t bind_lane_order(vr::LaneOrder& L, uint32_t gx, uint32_t gy, uint64_t 
     return hipMallocAsync((void**)&v.pcost, sizeof(uint32_t) * (size_t)v.LW * v.local_rows, st);
 }
 
-// VR_ORDER_CHECK (debugging): read a new work order back and report whether it is a
-// permutation of the grid.  (getenv per order build: off the steady-state path.)
-void order_check(const vr::WorkOrder& W, uint32_t slot, uint32_t gx, uint32_t gy) {
-    if (!std::getenv("VR_ORDER_CHECK")) return;
-    const uint32_t n = gx * gy;
-    std::vector<uint32_t> h(n), c(2 * (size_t)n);
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(h.data(), W.order, 4 * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(c.data(), W.cost, 8 * (size_t)n, hipMemcpyDeviceToHost);
-    std::vector<int> seen(n, 0);
-    int bad = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t t = (h[i] >> 16) * gx + (h[i] & 0xFFFFu);
-        if ((h[i] & 0xFFFFu) >= gx || t >= n || seen[t]++) ++bad;
-    }
-    fprintf(stderr, "[order] slot %u grid %ux%u n %u bad %d first %08x %08x cost0 %u %u\n", slot, gx, gy, n, bad, h[0],
-            n > 1 ? h[1] : 0u, c[0], c[1]);
-}
-
 // VR_HOST_PROF (measurement builds only, profiles/build_variant.sh -- -DVR_HOST_PROF): host
 // clock stamps at the stages of each launch, fetched with vr_host_prof_fetch.
 #ifdef VR_HOST_PROF
@@ -498,25 +482,30 @@ int launch(const vr_scene* s, vr_algo algo, uint32_t kernel, uint32_t schedule, 
         S.lane.learned(gx, gy, key, e == hipSuccess);
         D.uses[1] += e == hipSuccess;
         S.work.relaned = !with_costs;
-        if (e == hipSuccess && D.capture_lane) {     // (tests only: waits for the stream)
-            D.capture_lane = false;
-            SlotRing::Dev::LaneCapture& C = D.lane_capture;
-            C.LW = v.LW, C.rows = v.local_rows, C.gx = gx, C.gy = gy;
-            C.pcost.resize((size_t)v.LW * v.local_rows);
-            C.perm.resize(vr::perm_bytes(gx, gy));
-            e = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = hipMemcpy(C.pcost.data(), v.pcost, sizeof(uint32_t) * C.pcost.size(), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(C.perm.data(), S.lane.perm, C.perm.size(), hipMemcpyDeviceToHost);
-        }
     }
+    const bool capture = e == hipSuccess && relane && D.capture_lane;
     if (e == hipSuccess && (remake || with_costs)) {
         // (on a side stream instead -- one more stream than the box's 4 hardware queues
         // serialised the two render streams: C2 0.1124 -> 0.1277 ms per frame in flight,
         // profiles/r03/ab_order_C2_C3.txt)
         e = vr::launch_order(S.work.cost, n, gx, S.work.order, st);
-        order_check(S.work, lease.idx, gx, gy);
         S.work.learned(gx, gy, key, e == hipSuccess);
         D.uses[3] += e == hipSuccess;
+    }
+    if (capture && e == hipSuccess) {     // (tests only: waits for the stream)
+        D.capture_lane = false;
+        SlotRing::Dev::LaneCapture& C = D.lane_capture;
+        C.LW = v.LW, C.rows = v.local_rows, C.gx = gx, C.gy = gy;
+        C.pcost.resize((size_t)v.LW * v.local_rows);
+        C.perm.resize(vr::perm_bytes(gx, gy));
+        // (the work order only when this launch made it from perm_kernel's costs)
+        C.cost.resize(with_costs ? (size_t)vr::kWavesPerTileGroup * n : 0);
+        C.order.resize(with_costs ? (size_t)n : 0);
+        e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(C.pcost.data(), v.pcost, sizeof(uint32_t) * C.pcost.size(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(C.perm.data(), S.lane.perm, C.perm.size(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_costs) e = hipMemcpy(C.cost.data(), S.work.cost, sizeof(uint32_t) * C.cost.size(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_costs) e = hipMemcpy(C.order.data(), S.work.order, sizeof(uint32_t) * C.order.size(), hipMemcpyDeviceToHost);
     }
     if (v.pcost) {      // (a relaning launch's per-pixel walk lengths: transient)
         const hipError_t ef = hipFreeAsync(v.pcost, st);
@@ -710,6 +699,108 @@ int vr_debug_lane_order(int device, uint32_t info[8], uint32_t* pcost, uint64_t 
         if (perm_bytes != C.perm.size()) return fail(VR_E_INVALID, "perm_bytes is not the captured order's size");
         std::memcpy(perm, C.perm.data(), C.perm.size());
     }
+    return VR_OK;
+}
+
+int vr_debug_work_order(int device, uint32_t* cost, uint64_t cost_words, uint32_t* order, uint64_t order_words) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    SlotRing::Dev& D = g_defer_ring.dev[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    const SlotRing::Dev::LaneCapture& C = D.lane_capture;
+    if (C.order.empty())
+        return fail(VR_E_INVALID, "no work order captured (vr_debug_capture_lane_order, then a repeated view whose "
+                                  "launch makes its work order from the lane order's costs)");
+    if (cost) {
+        if (cost_words != C.cost.size()) return fail(VR_E_INVALID, "cost_words is not 2 * info[2] * info[3]");
+        std::memcpy(cost, C.cost.data(), sizeof(uint32_t) * C.cost.size());
+    }
+    if (order) {
+        if (order_words != C.order.size()) return fail(VR_E_INVALID, "order_words is not info[2] * info[3]");
+        std::memcpy(order, C.order.data(), sizeof(uint32_t) * C.order.size());
+    }
+    return VR_OK;
+}
+
+namespace {
+// A scratch device buffer of a test hook, freed when it returns.  An output (fill) is followed
+// by kGuardBytes more and all of it is filled with 0xFF bytes before the kernel runs: fetch
+// copies the output back and reports whether the guard behind it is still as filled (a kernel
+// that wrote past its output is caught inside memory the hook owns).
+struct Scratch {
+    static constexpr size_t kGuardBytes = 256;
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~Scratch() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, n + kGuardBytes); }
+    hipError_t fill() { return hipMemset(p, 0xFF, bytes + kGuardBytes); }
+    hipError_t fetch(void* host, bool& guard_ok) {
+        unsigned char g[kGuardBytes];
+        hipError_t e = hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(g, (const char*)p + bytes, kGuardBytes, hipMemcpyDeviceToHost);
+        for (size_t i = 0; e == hipSuccess && i < kGuardBytes; ++i) guard_ok = guard_ok && g[i] == 0xFFu;
+        return e;
+    }
+};
+}  // namespace
+
+int vr_debug_lane_order_from(int device, const uint32_t* pcost_host, uint32_t LW, uint32_t rows, uint32_t info[8],
+                             uint8_t* perm, uint64_t perm_bytes, uint32_t* cost, uint64_t cost_words) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    if (!info) return fail(VR_E_INVALID, "info is NULL");
+    if (LW == 0 || rows == 0 || LW > 65536 || rows > 65536) return fail(VR_E_INVALID, "bad frame size");
+    vr::KView v{};
+    v.LW = LW;
+    v.local_rows = rows;
+    uint32_t gx = 0, gy = 0;
+    vr::march_grid(v, gx, gy);
+    const vr::LaneShape sh = vr::lane_shape();
+    const uint32_t words[8] = {LW, rows, gx, gy, sh.block_x, sh.block_y, sh.entry_bytes, sh.seat};
+    std::memcpy(info, words, sizeof words);
+    if (!pcost_host && !perm && !cost) return VR_OK;       // (the sizes only)
+    if (!pcost_host || !perm || !cost) return fail(VR_E_INVALID, "pcost_host, perm or cost is NULL");
+    const size_t nperm = vr::perm_bytes(gx, gy), ncost = (size_t)vr::kWavesPerTileGroup * gx * gy;
+    if (perm_bytes != nperm) return fail(VR_E_INVALID, "perm_bytes is not the order's size");
+    if (cost_words != ncost) return fail(VR_E_INVALID, "cost_words is not 2 * info[2] * info[3]");
+    DeviceGuard dg(device);
+    const size_t npc = sizeof(uint32_t) * (size_t)LW * rows;
+    Scratch dp, dperm, dcost;
+    hipError_t e = dp.alloc(npc);
+    if (e == hipSuccess) e = dperm.alloc(nperm);
+    if (e == hipSuccess) e = dcost.alloc(sizeof(uint32_t) * ncost);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(lane order scratch)");
+    e = hipMemcpy(dp.p, pcost_host, npc, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dperm.fill();
+    if (e == hipSuccess) e = dcost.fill();
+    if (e == hipSuccess)
+        e = vr::launch_perm((const uint32_t*)dp.p, LW, rows, gx, gy, (uint8_t*)dperm.p, (uint32_t*)dcost.p, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    bool guard_ok = true;
+    if (e == hipSuccess) e = dperm.fetch(perm, guard_ok);
+    if (e == hipSuccess) e = dcost.fetch(cost, guard_ok);
+    if (e != hipSuccess) return hip_fail(e, "vr_debug_lane_order_from");
+    if (!guard_ok) return fail(VR_E_HIP, "vr_debug_lane_order_from: perm_kernel wrote past perm or cost (guard bytes changed)");
+    return VR_OK;
+}
+
+int vr_debug_work_order_from(int device, const uint32_t* cost_host, uint32_t columns, uint32_t groups, uint32_t* order) {
+    if (device < 0 || device >= 64) return fail(VR_E_INVALID, "device index out of range");
+    if (!cost_host || !order) return fail(VR_E_INVALID, "cost_host or order is NULL");
+    if (columns == 0 || columns > 4096 || groups == 0 || groups % columns != 0 || groups / columns > 8192)
+        return fail(VR_E_INVALID, "bad grid (columns 1..4096, groups a multiple of columns, at most 8192 rows)");
+    DeviceGuard dg(device);
+    const size_t ncost = sizeof(uint32_t) * (size_t)vr::kWavesPerTileGroup * groups, nord = sizeof(uint32_t) * (size_t)groups;
+    Scratch dcost, dord;
+    hipError_t e = dcost.alloc(ncost);
+    if (e == hipSuccess) e = dord.alloc(nord);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(work order scratch)");
+    e = hipMemcpy(dcost.p, cost_host, ncost, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dord.fill();
+    if (e == hipSuccess) e = vr::launch_order((const uint32_t*)dcost.p, groups, columns, (uint32_t*)dord.p, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    bool guard_ok = true;
+    if (e == hipSuccess) e = dord.fetch(order, guard_ok);
+    if (e != hipSuccess) return hip_fail(e, "vr_debug_work_order_from");
+    if (!guard_ok) return fail(VR_E_HIP, "vr_debug_work_order_from: order_kernel wrote past order (guard bytes changed)");
     return VR_OK;
 }
 

@@ -293,8 +293,15 @@ __global__ __launch_bounds__(64 * kTilesX * kTilesY, (TileWaves<ALGO, HI>::value
         const size_t at = (size_t)(p >> 16) * v.LW + (p & 0xFFFFu);
         v.out[at] = c;
         if (v.pcost) {                            // the pixel's walk lengths, for the next lane order
+            // A pixel handed to the crawl pass (shade: 0 bytes after a walk) stores the half that
+            // was walking saturated, however it was handed over: a crawl record leaves
+            // kDeferredIters in iters, a longest-axis jump crawl and a walk past the budget their
+            // count so far.  (No shadow iterations yet: the primary walk was the one.)
             const uint32_t p0 = tile_prim()[threadIdx.x];
-            v.pcost[at] = min(p0, 0xFFFFu) << 16 | min(iters - p0, 0xFFFFu);
+            const bool deferred = bytes == 0u && iters != 0u;
+            const uint32_t pp = deferred && iters == p0 ? 0xFFFFu : min(p0, 0xFFFFu);
+            const uint32_t ss = deferred && iters != p0 ? 0xFFFFu : min(iters - p0, 0xFFFFu);
+            v.pcost[at] = pp << 16 | ss;
         }
     }
     if (COUNT) add_bytes(v, lane, bytes);

@@ -771,7 +771,7 @@ def debug_lane_order(device: int = 0):
     import numpy as np
     raw = (ctypes.c_uint32 * 8)()
     check(lib().vr_debug_lane_order(int(device), raw, None, 0, None, 0), "vr_debug_lane_order")
-    info = dict(zip(("LW", "rows", "gx", "gy", "block_x", "block_y", "entry_bytes", "seat"), (int(x) for x in raw)))
+    info = dict(zip(LANE_INFO, (int(x) for x in raw)))
     n = info["block_x"] * info["block_y"]
     blocks = -(-info["LW"] // info["block_x"]) * (-(-info["rows"] // info["block_y"]))
     pcost = np.empty((info["rows"], info["LW"]), dtype=np.uint32)
@@ -779,6 +779,61 @@ def debug_lane_order(device: int = 0):
     check(lib().vr_debug_lane_order(int(device), raw, c_void_p(pcost.ctypes.data), pcost.size,
                                     c_void_p(perm.ctypes.data), perm.nbytes), "vr_debug_lane_order")
     return info, pcost, perm
+
+
+LANE_INFO = ("LW", "rows", "gx", "gy", "block_x", "block_y", "entry_bytes", "seat")
+
+
+def debug_work_order(device: int = 0):
+    """Test hook (vr_debug_work_order): the captured launch's (cost, order) -- cost a (gy, gx, 2)
+    uint32 array, each wave's max(primary) + max(shadow) walk length under the captured lane
+    order, order the gx * gy words (row << 16 | column) of the work order made from them.
+    Raises VrError when the captured launch made no work order from those costs."""
+    import numpy as np
+    info, _, _ = debug_lane_order(device)
+    check(lib().vr_debug_work_order(int(device), None, 0, None, 0), "vr_debug_work_order")
+    cost = np.empty((info["gy"], info["gx"], 2), dtype=np.uint32)
+    order = np.empty(info["gy"] * info["gx"], dtype=np.uint32)
+    check(lib().vr_debug_work_order(int(device), c_void_p(cost.ctypes.data), cost.size,
+                                    c_void_p(order.ctypes.data), order.size), "vr_debug_work_order")
+    return cost, order
+
+
+def debug_lane_order_from(pcost, device: int = 0):
+    """Test hook (vr_debug_lane_order_from): perm_kernel run on the caller's (rows, LW) uint32
+    walk lengths (primary << 16 | shadow) -> (info, perm, cost), as debug_lane_order and
+    debug_work_order return them; whatever the kernel left unwritten is 0xFF bytes."""
+    import numpy as np
+    pcost = np.ascontiguousarray(pcost, dtype=np.uint32)
+    if pcost.ndim != 2:
+        raise ValueError("pcost must be a (rows, LW) array")
+    rows, LW = pcost.shape
+    raw = (ctypes.c_uint32 * 8)()
+    check(lib().vr_debug_lane_order_from(int(device), None, LW, rows, raw, None, 0, None, 0), "vr_debug_lane_order_from")
+    info = dict(zip(LANE_INFO, (int(x) for x in raw)))
+    n = info["block_x"] * info["block_y"]
+    blocks = -(-info["LW"] // info["block_x"]) * (-(-info["rows"] // info["block_y"]))
+    perm = np.empty((blocks, n), dtype=np.uint8 if info["entry_bytes"] == 1 else np.uint16)
+    cost = np.empty((info["gy"], info["gx"], 2), dtype=np.uint32)
+    check(lib().vr_debug_lane_order_from(int(device), c_void_p(pcost.ctypes.data), LW, rows, raw,
+                                         c_void_p(perm.ctypes.data), perm.nbytes, c_void_p(cost.ctypes.data), cost.size),
+          "vr_debug_lane_order_from")
+    return info, perm, cost
+
+
+def debug_work_order_from(cost, columns: int, device: int = 0):
+    """Test hook (vr_debug_work_order_from): order_kernel run on the caller's costs (two words
+    per tile group, groups in rows of `columns`) -> the order's words (row << 16 | column);
+    whatever the kernel left unwritten is 0xFFFFFFFF."""
+    import numpy as np
+    cost = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+    if cost.size % 2:
+        raise ValueError("cost must hold two words per tile group")
+    groups = cost.size // 2
+    order = np.empty(groups, dtype=np.uint32)
+    check(lib().vr_debug_work_order_from(int(device), c_void_p(cost.ctypes.data), int(columns), groups,
+                                         c_void_p(order.ctypes.data)), "vr_debug_work_order_from")
+    return order
 
 
 ORDER_USES = ("launches", "lane_orders_made", "lane_order_uses", "work_orders_made", "work_order_uses",
