@@ -127,6 +127,16 @@ __device__ __forceinline__ float bit_select(uint32_t m, float a, float b) {
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
     return r;
 }
+// The same in C++ for the walk loops (see Ctx::cell): one v_bfi_b32 / v_bitop3_b32 when a is
+// not a constant the compiler knows -- the caller passes it through walk_const once per walk
+// (a known constant is folded into an xor and a second operation).
+__device__ __forceinline__ float bit_sel(uint32_t m, float a, float b) {
+    return __uint_as_float((m & __float_as_uint(a)) | (~m & __float_as_uint(b)));
+}
+__device__ __forceinline__ float walk_const(float c) {
+    asm("" : "+v"(c));
+    return c;
+}
 
 // u32 `h % M` for a divisor fixed over a walk: minv = floor(2^32 / M) (2^32 - 1
 // for M = 1) gives q' = mulhi(h, minv) in {q - 1, q}, so r' = h - q' M is in
@@ -277,6 +287,14 @@ struct Ctx {
         return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(s.vcs_mask) +
                                                ((reg << 16) | (slot << 7) | (w << 3)));
     }
+    // The mask word at byte offset off of the scene's mask array (word_offset's), loaded as a
+    // two-component vector: its halves are then plain 32-bit values (from a 64-bit load the
+    // compiler tests the upper half, absent(), with a 64-bit compare).
+    __device__ __forceinline__ Blk mask_at(uint32_t off) const {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 w = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(s.vcs_mask) + off);
+        return Blk{w.x, w.y};
+    }
     __device__ __forceinline__ static uint32_t word_index(uint32_t x, uint32_t y, uint32_t z) {   // x,y,z < 64
         // v_bfe + 3 v_lshl_or; the two v_and (y & 0x38, z & 0x38) are shared
         // with the cluster-skip planes of the walk
@@ -286,6 +304,32 @@ struct Ctx {
         const uint32_t hi = lshl_or(z & 0x38u, 3u, y & 0x38u);
         return lshl_or(hi, 4u, lo);
     }
+    // The walk loops' forms.  The compiler cannot see into an asm statement, so on gfx950 it
+    // pads with one s_nop every place where the next vector instruction -- or the next asm
+    // statement -- reads an asm statement's result (it must assume the result is forwarded
+    // late).  One such pad holds the wave for an issue turn, and the loop head's sit on the
+    // chain to the mask load.  So inside a walk loop no asm result has a vector instruction as
+    // its reader (profiles/pads/):
+    //  - cell: the voxel of a coordinate in [0, 64) (not NaN), which every coordinate is at a
+    //    walk loop's top -- by the walk's entry test and the exit test of the iteration before.
+    //    There the plain cast is f2i's v_cvt_i32_f32, made by the compiler.
+    //  - word_offset: base | word_index(x, y, z) << SH as ONE statement of four v_lshl_or whose
+    //    only reader is the load's address: ((z38 << 3 | y38) << 3 | x) << 1 | y2, the same
+    //    index (the fields do not overlap: x < 64).  The result is early-clobber: it is
+    //    written before x, y2 and base are read.
+    //  - word_bit5c and bit_sel are plain C++ that selects two and one instruction.
+    __device__ __forceinline__ static int32_t cell(float f) { return (int32_t)f; }
+    template <uint32_t SH>
+    __device__ __forceinline__ static uint32_t word_offset(uint32_t x, uint32_t y, uint32_t z, uint32_t base) {   // x,y,z < 64
+        uint32_t r;
+        asm("v_lshl_or_b32 %0, %1, 3, %2\n\t"
+            "v_lshl_or_b32 %0, %0, 3, %3\n\t"
+            "v_lshl_or_b32 %0, %0, 1, %4\n\t"
+            "v_lshl_or_b32 %0, %0, %6, %5"
+            : "=&v"(r)
+            : "v"(z & 0x38u), "v"(y & 0x38u), "v"(x), "v"(__builtin_amdgcn_ubfe(y, 2u, 1u)), "v"(base), "i"(SH));
+        return r;
+    }
     // Bit of an in-region voxel in its mask word, in the low 5 bits only
     // ((y&3)<<3 | z&7 there; v_bfe and shifts read just those): one v_bfi.
     __device__ __forceinline__ static uint32_t word_bit5(uint32_t y, uint32_t z) {
@@ -293,7 +337,8 @@ struct Ctx {
         asm("v_bfi_b32 %0, 7, %1, %2" : "=v"(r) : "v"(z), "v"(y << 3));
         return r;
     }
-
+    // (the walk loops' form, the same value: v_lshlrev + v_and_or)
+    __device__ __forceinline__ static uint32_t word_bit5c(uint32_t y, uint32_t z) { return (y << 3) | (z & 7u); }
     // doesVoxelSpaceExist (StorageStructure.cuh:29-32,49-52) ->
     // VoxelClusterStore::doesClusterExist (VoxelClusterStore.cuh:93-99).
     // VCS: one 8-B read of the mask word the later lookup of this voxel needs,

@@ -354,29 +354,37 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                         // (an arm: the ray's, uniform)
                         const bool okw = kArm ? aw->okw : __builtin_amdgcn_ballot_w64(!walk_ok) == 0;
                         VR_DIAG_COUNT((SHADOW ? 4 : 0) + (SX == 0 ? 1 : 0));   // walk entries
+                        const float neg_eps = walk_const(-kEps);   // (bit_sel's)
                         for (;;) {
                             VR_DIAG_COUNT((SHADOW ? 6 : 2) + (SX == 0 ? 1 : 0));   // loop iterations
-                            const int32_t vx = f2i(o.x), vy = f2i(o.y), vz = f2i(o.z);
+                            // (o is in the region here, so the plain cast is f2i; the mask word's
+                            // byte offset is one statement read by the load alone: see Ctx::cell)
+                            const int32_t vx = this->cell(o.x), vy = this->cell(o.y), vz = this->cell(o.z);
                             this->count(4);
-                            const uint32_t wi = this->word_index((uint32_t)vx, (uint32_t)vy, (uint32_t)vz);
+                            const uint32_t woff = this->template word_offset<3u>((uint32_t)vx, (uint32_t)vy, (uint32_t)vz, moff);
+                            [[maybe_unused]] const uint32_t wi = (woff >> 3) & 8191u;   // (crawl pass, COUNT)
                             if constexpr (CRAWL) {
                                 // (crawl pass) cluster slot wi >> 4 absent per the LDS bits: no load
                                 const bool pres = !bits || ((bits[wi >> 9] >> ((wi >> 4) & 31u)) & 1u);
                                 if (COUNT && !pres) ++this->nl;   // counted above, never loaded
                                 blk = Blk{0u, kNone};
                                 if (pres)
-                                    blk = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(s.vcs_mask) +
-                                                                          (moff | (wi << 3)));
+                                    blk = this->mask_at(woff);
                             } else {
-                                blk = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(s.vcs_mask) +
-                                                                      (moff | (wi << 3)));
+                                blk = this->mask_at(woff);
                             }
                             __builtin_amdgcn_sched_barrier(0);   // issue the load before the planes
                             // both candidate planes, computed while the mask word is in
-                            // flight and materialised (with the whole 8-B word: one load)
+                            // flight and materialised before the wait for it (the second
+                            // barrier; the word itself is no operand of the asm, whose results
+                            // the next instruction, the compare of blk.y, would then read)
 #if VR_UNIFORM_SKIP
                             float vX = plane_v<SX>(o.x, gx, ex), vY = plane_v<SY>(o.y, gy, ey), vZ = plane_v<SZ>(o.z, gz, ez);
-                            asm("" : "+v"(vX), "+v"(vY), "+v"(vZ), "+v"(blk.x), "+v"(blk.y));
+                            asm("" : "+v"(vX), "+v"(vY), "+v"(vZ));
+                            // (the count's add as asm: loop strength reduction otherwise keeps two
+                            // counters; here, so that its reader -- the exit test -- is far from it)
+                            asm("v_add_u32 %0, 1, %0" : "+v"(ic));
+                            __builtin_amdgcn_sched_barrier(0);
                             const bool skip = absent(blk);
                             float nX = vX, nY = vY, nZ = vZ;
                             const bool any_skip = __builtin_amdgcn_ballot_w64(skip) != 0;
@@ -384,7 +392,9 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                 float cX = (float)((vx & 0x38) + plane_c8<SX>(cx8)), cY = (float)((vy & 0x38) + plane_c8<SY>(cy8)),
                                       cZ = (float)((vz & 0x38) + plane_c8<SZ>(cz8));
                                 nX = skip ? cX : vX; nY = skip ? cY : vY; nZ = skip ? cZ : vZ;
-                                asm volatile("" : "+v"(nX), "+v"(nY), "+v"(nZ));
+                                // (keeps the selects in this block; the values are inputs only:
+                                // as results, the step's subtractions would read an asm's)
+                                asm volatile("" : : "v"(nX), "v"(nY), "v"(nZ));
                             }
 #else
                             float vX = plane_v<SX>(o.x, gx, ex), vY = plane_v<SY>(o.y, gy, ey), vZ = plane_v<SZ>(o.z, gz, ez);
@@ -392,6 +402,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                             float cX = (float)((vx & 0x38) + plane_c8<SX>(cx8)), cY = (float)((vy & 0x38) + plane_c8<SY>(cy8)),
                                   cZ = (float)((vz & 0x38) + plane_c8<SZ>(cz8));
                             asm("" : "+v"(vX), "+v"(vY), "+v"(vZ), "+v"(cX), "+v"(cY), "+v"(cZ), "+v"(blk.x), "+v"(blk.y));
+                            asm("v_add_u32 %0, 1, %0" : "+v"(ic));   // (the count: see above)
                             const bool skip = absent(blk);
                             const bool any_skip = __builtin_amdgcn_ballot_w64(skip) != 0;
 #endif
@@ -403,7 +414,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                 else if (bs == __builtin_amdgcn_read_exec()) VR_DIAG_COUNT(SHADOW ? 25 : 23);
                             }
 #endif
-                            bit = this->word_bit5((uint32_t)vy, (uint32_t)vz);
+                            bit = this->word_bit5c((uint32_t)vy, (uint32_t)vz);
                             // 0 or ~0 (an absent cluster's words have no bits set)
                             const uint32_t fm = (uint32_t)__builtin_amdgcn_sbfe((int32_t)blk.x, bit, 1u);
                             found = fm != 0u;
@@ -428,7 +439,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                         VR_DIAG_COUNT(33);     // VCS walk, one divisor: IEEE fallback
                                         sMin = bad ? am / fabsf(d.x) : sMin;
                                         crawl = bad & walk_ok & skip & (sMin == 0.0f) &
-                                                (CRAWL ? ic + 1u - (0x42800000u - kBudget) >= crawl_after : !crawl_off);
+                                                (CRAWL ? ic - (0x42800000u - kBudget) >= crawl_after : !crawl_off);
                                         if (CRAWL && crawl) { qx = vx; qy = vy; qz = vz; }
                                     }
                                 }
@@ -444,7 +455,7 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                                         // a skip step with t = 0 (its plane axis has n = 0, so it is
                                         // always on this branch): the ray creeps through an empty cluster
                                         crawl = bad & walk_ok & skip & (fminf(sX, fminf(sY, sZ)) == 0.0f) &
-                                                (CRAWL ? ic + 1u - (0x42800000u - kBudget) >= crawl_after : !crawl_off);
+                                                (CRAWL ? ic - (0x42800000u - kBudget) >= crawl_after : !crawl_off);
                                         if (CRAWL && crawl) { qx = vx; qy = vy; qz = vz; }
                                     }
                                 }
@@ -454,12 +465,11 @@ struct Walker : Ctx<STORE, COUNT, ExactWalk<STORE, CRAWL>::value ? kCrawlBudget 
                             }
                             // A hit keeps o unstepped: its step length becomes (-EPSILON) + EPSILON
                             // = +0 exactly, and o + (+0 * d) = o (o is never -0, d is finite in here).
-                            const float ts = bit_select(fm, -kEps, sMin) + kEps;
+                            const float ts = bit_sel(fm, neg_eps, sMin) + kEps;
                             o = EQ ? add(o, f3{ts * d.x, ts * d.x, ts * d.x}) : add(o, scl(ts, d));
                             // One unsigned compare for hit, region exit (in_region_bits_nz of the
-                            // stepped position) and the budget (iters >= kBudget):
-                            // (the add as asm: loop strength reduction otherwise keeps two counters)
-                            asm("v_add_u32 %0, 1, %0" : "+v"(ic));
+                            // stepped position) and the budget (iters >= kBudget; ic counts this
+                            // iteration already):
                             const uint32_t ev = max(max(max(max(__float_as_uint(o.x), __float_as_uint(o.y)), __float_as_uint(o.z)),
                                                         ic), fm);
                             if (ev >= 0x42800000u || crawl) break;
