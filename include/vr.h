@@ -691,6 +691,66 @@ int vr_render_count(const vr_scene* s, vr_algo algo, const vr_camera* cam, const
  * (3 bytes per pixel, R = word >> 16 truncated to 8 bits), on the device. */
 int vr_pack_rgb8(const uint32_t* words_dev, uint8_t* rgb_dev, uint64_t n_pixels, void* stream);
 
+/* Supersampled frames: the render at `samples` x `samples` samples per pixel, box-filtered.
+ *
+ * samples = S in {1, 2, 4, 8} per axis, N = S * S.  The FINE FRAME of a W x H frame is the
+ * (S * W) x (S * H) render of the same scene, algorithm, camera, lighting, translation and scale:
+ * vr_render's frame of that size, word for word.  Pixel (x, y) of the RESOLVED FRAME has, for each
+ * channel c (R = bits 16-23, G = bits 8-15, B = bits 0-7 of a word; bits 24-31 of a fine word are
+ * dropped, as vr_shade_lights drops them),
+ *
+ *   out_c(x, y) = (sum over 0 <= i, j < S of c(fine[(S * y + j) * (S * W) + S * x + i]) + N / 2) >> log2(N)
+ *
+ * packed R << 16 | G << 8 | B: the mean of the pixel's N samples, rounded half up.  The arithmetic
+ * is of integers only, so no order of summation can matter.  With S = 1 the resolved word is the
+ * fine word with bits 24-31 cleared: vr_render's word whenever that word is below 2^24.
+ * (The reference's v = ((H - y) + 0.5) / H puts row 0 one row above the image plane; in the fine
+ * frame that is one FINE row, so the resolved frame sits (S - 1) / (2 S) of a pixel lower than
+ * the one-sample frame.  Deliberate: the resolved frame is exactly "the bigger render,
+ * box-filtered")
+ *
+ * vr_aa_fine_words: the words of the fine frame of `rows` rows of a frame `width` wide,
+ * (S * width) * (S * rows); 0 for arguments vr_render_aa rejects (samples not 1, 2, 4 or 8, width
+ * outside 1..65536, rows above 65536, S * width or S * rows above 65536). */
+uint64_t vr_aa_fine_words(uint32_t width, uint32_t rows, uint32_t samples);
+
+/* The filter alone: resolves the fine frame at fine_dev -- (S * width) x (S * rows) words, row-major,
+ * already on the current device: a vr_render, a frame of vr_shade_lights words or an assembled
+ * multi-GPU frame -- to width x rows pixels.  out_dev (or NULL) receives the packed words,
+ * width * rows of them; out_rgb8_dev (or NULL) the same pixels as RGB8, 3 bytes per pixel, R
+ * first, as vr_pack_rgb8 writes them.  With both, both come from one read of the fine frame.  One
+ * kernel on `stream`, asynchronous; allocates nothing.  Every fine word is read once, with 16-byte
+ * loads when fine_dev is 16-byte aligned (and, at S = 2, width is even); a fine_dev that is only
+ * 4-byte aligned is accepted and read word by word.
+ *
+ * VR_E_INVALID, before any device work: fine_dev NULL; both outputs NULL; samples not 1, 2, 4 or 8;
+ * width or rows outside 1..65536; S * width or S * rows above 65536; fine_dev or out_dev not
+ * 4-byte aligned; a stream that is capturing a HIP graph. */
+int vr_resolve(const uint32_t* fine_dev, uint32_t width, uint32_t rows, uint32_t samples,
+               uint32_t* out_dev /* or NULL */, uint8_t* out_rgb8_dev /* or NULL */, void* stream);
+
+/* Rows [row_begin, row_end) of the resolved width x height frame.  Renders fine rows
+ * [S * row_begin, S * row_end) of the fine frame into fine_dev through vr_render -- an ordinary
+ * render launch of the (S * width) x (S * height) view, so a repeated view learns and uses its
+ * orders as under vr_render -- and resolves them on the same stream into out_dev
+ * ((row_end - row_begin) * width words) and/or out_rgb8_dev (3 bytes per pixel), as vr_resolve.
+ * Asynchronous, as vr_render.  Afterwards fine_dev holds those fine rows, packed from its start.
+ *
+ * The caller owns fine_dev (fine_words words, at least vr_aa_fine_words(width, row_end -
+ * row_begin, samples)) and must not reuse it while a launch that uses it is in flight on another
+ * stream: two frames in flight need two buffers.
+ *
+ * VR_E_INVALID, every check before any device work: s, cam, lit, translation or fine_dev NULL;
+ * both outputs NULL; samples not 1, 2, 4 or 8; width or height outside 1..65536; S * width or
+ * S * height above 65536; row_begin <= row_end <= height violated (an empty range is VR_OK and
+ * does nothing); fine_words too small; an unknown algorithm; fine_dev or out_dev not 4-byte
+ * aligned; a stream that is capturing a HIP graph. */
+int vr_render_aa(const vr_scene* s, vr_algo algo, const vr_camera* cam, const vr_lighting* lit,
+                 const float translation[3], uint32_t scale, uint32_t width, uint32_t height,
+                 uint32_t samples, uint32_t row_begin, uint32_t row_end,
+                 uint32_t* fine_dev, uint64_t fine_words,
+                 uint32_t* out_dev /* or NULL */, uint8_t* out_rgb8_dev /* or NULL */, void* stream);
+
 /* ImageWriter::writeImage(filename, image, width, height, colorChannels)
  * (ImageWriter.cpp:8-16, stbi_write_png with tightly packed rows): 8-bit PNG
  * of 1-4 channels from HOST memory. Row chunks are deflated on parallel

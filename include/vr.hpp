@@ -144,6 +144,28 @@ inline void runRaymarchingKernel(uint32_t width, uint32_t height, RayMarchAlgori
           "runRaymarchingKernel");
 }
 
+// vr_render_aa: the frame at samples x samples (1, 2, 4 or 8 per axis) samples per pixel, box-filtered
+// with round half up -- runRaymarchingKernel of the (samples * width) x (samples * height) frame
+// into fineDev (vr_aa_fine_words(width, height, samples) words, the caller's), resolved on the same
+// stream into framebufferDev (width * height words) and/or rgb8Dev (3 bytes per pixel); asynchronous.
+inline void runRaymarchingKernelAA(uint32_t width, uint32_t height, uint32_t samples, RayMarchAlgorithm algo,
+                                   const Camera& camera, const VoxelSceneInfo& info, const DeviceScene& scene,
+                                   const vr_lighting& lighting, uint32_t* fineDev, uint32_t* framebufferDev,
+                                   uint8_t* rgb8Dev = nullptr, void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    check(vr_render_aa(scene.get(), (vr_algo)algo, &camera.raw(), &lighting, t, info.scale, width, height, samples, 0,
+                       height, fineDev, vr_aa_fine_words(width, height, samples), framebufferDev, rgb8Dev, stream),
+          "runRaymarchingKernelAA");
+}
+
+// vr_resolve: the filter alone, for any fine frame of (samples * width) x (samples * rows) words
+// already on the device (a render, a frame of shadeLights words, an assembled multi-GPU frame);
+// asynchronous, allocates nothing.
+inline void resolve(const uint32_t* fineDev, uint32_t width, uint32_t rows, uint32_t samples, uint32_t* framebufferDev,
+                    uint8_t* rgb8Dev = nullptr, void* stream = nullptr) {
+    check(vr_resolve(fineDev, width, rows, samples, framebufferDev, rgb8Dev, stream), "resolve");
+}
+
 // vr_pick: the hit behind each pixel (px[i], py[i]) of the frame runRaymarchingKernel renders
 // for the same arguments -- the voxel (what vr_scene_edit takes), the reference's shading
 // normal and the hit point.  Host arrays in, host records out; returns when they are written.

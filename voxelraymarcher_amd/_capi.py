@@ -145,6 +145,11 @@ SIGNATURES = {
     "vr_camera_rays": (c_int, [c_int, POINTER(VrCamera), c_uint32, c_uint32, c_void_p, c_void_p, c_size_t, c_int,
                                c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
+    "vr_aa_fine_words": (c_uint64, [c_uint32, c_uint32, c_uint32]),
+    "vr_resolve": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "vr_render_aa": (c_int, [c_void_p, c_int, POINTER(VrCamera), POINTER(VrLighting), POINTER(c_float), c_uint32,
+                             c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p,
+                             c_void_p]),
     "vr_synth_generate": (c_int, [POINTER(VrSynthParams), POINTER(c_int32), POINTER(c_uint32), c_size_t,
                                   POINTER(c_size_t)]),
     "vr_vox_read": (c_int, [c_char_p, POINTER(c_int32), POINTER(c_uint32), c_size_t, POINTER(c_size_t)]),

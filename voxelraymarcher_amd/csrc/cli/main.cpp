@@ -34,6 +34,11 @@
 //                                 first, then the added ones, the terms summed per channel with a
 //                                 clamp at 255 -- and a line "lights <N> ambient <r> <g> <b>" is
 //                                 printed before "Wrote"; not with --gpus
+//                   [--aa S]     (S = 1, 2, 4 or 8 samples per axis: output.png is the resolved frame --
+//                                 the (S * width) x (S * height) render box-filtered with round half
+//                                 up, vr_render_aa; with --add-light / --ambient the lights frame is
+//                                 made at that size and resolved, vr_resolve; the time printed is
+//                                 the fine render plus the filter; not with --gpus)
 // Defaults follow Main.cu: VCS unless "hashtable", longest axis unless
 // "original" (:45-68), 1920x1080 (:195-196), camera (6,2,6)->(0,0,-1) fov 60
 // (:199), translation 0 (:215), scene file resources/scene.vox (:96-103).
@@ -153,6 +158,7 @@ int main(int argc, char* argv[]) {
     std::string scene_path = "resources/scene.vox", out_path = "output.png", vxb_path;
     uint32_t width = 1920, height = 1080, synth = 0;
     int device = 0, repeat = 1, gpus = 0;
+    uint32_t aa = 0;                         // --aa S: samples per axis (0: not given)
     bool multi = false;                      // --gpus given: the RCCL-tiled frame
     bool shadows = true, point_light = false, has_dir = false;
     std::vector<uint32_t> pick_x, pick_y;    // --pick X,Y (repeatable)
@@ -181,6 +187,14 @@ int main(int argc, char* argv[]) {
         else if (a == "--device") device = std::atoi(next("--device"));
         else if (a == "--synth") synth = (uint32_t)std::strtoul(next("--synth"), nullptr, 10);
         else if (a == "--gpus") { multi = true; gpus = std::atoi(next("--gpus")); }
+        else if (a == "--aa") {
+            const char* v = next("--aa");
+            if (std::strcmp(v, "1") && std::strcmp(v, "2") && std::strcmp(v, "4") && std::strcmp(v, "8")) {
+                std::cerr << "--aa needs 1, 2, 4 or 8 (samples per axis)" << std::endl;
+                std::exit(2);
+            }
+            aa = (uint32_t)std::atoi(v);
+        }
         else if (a == "--repeat") repeat = std::max(1, std::atoi(next("--repeat")));
         else if (a == "--write-vxb") vxb_path = next("--write-vxb");
         else if (a == "--no-shadows") shadows = false;
@@ -252,7 +266,7 @@ int main(int argc, char* argv[]) {
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
                          "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
                          "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]... [--add-light DX,DY,DZ,R,G,B]... "
-                         "[--ambient R,G,B]" << std::endl;
+                         "[--ambient R,G,B] [--aa S]" << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -289,6 +303,10 @@ int main(int argc, char* argv[]) {
     const bool lights_frame = !added_lights.empty() || has_ambient;
     if (lights_frame && multi) {             // (the frame is one device's vr_shade_lights call)
         std::cerr << "ERROR: --add-light and --ambient shade a single-GPU frame: not with --gpus" << std::endl;
+        return 2;
+    }
+    if (aa && multi) {                       // (a resolved frame dealt over several GPUs: a later change)
+        std::cerr << "ERROR: --aa resolves a single-GPU frame: not with --gpus" << std::endl;
         return 2;
     }
     if (added_lights.size() + 1u > VR_MAX_LIGHTS) {
@@ -467,6 +485,18 @@ int main(int argc, char* argv[]) {
         }
         uint32_t* fb = nullptr;
         uint8_t* rgb = nullptr;
+        // --aa: the fine frame of S x S samples per pixel, resolved into fb
+        const uint32_t S = aa ? aa : 1u;
+        const uint64_t fine_words = aa ? vr_aa_fine_words(width, height, S) : 0;
+        uint32_t* fine = nullptr;
+        if (aa) {
+            if (fine_words == 0) {
+                std::cerr << "ERROR: --aa " << S << ": the fine frame of " << width << "x" << height
+                          << " is too large (at most 65536 samples per axis)" << std::endl;
+                return 2;
+            }
+            HIP_OK(hipMalloc(&fine, fine_words * 4));
+        }
         HIP_OK(hipMalloc(&fb, (size_t)width * height * 4));
         HIP_OK(hipMalloc(&rgb, (size_t)width * height * 3));
         hipEvent_t e0, e1;
@@ -475,7 +505,8 @@ int main(int argc, char* argv[]) {
         float best_ms = 1e30f;
         for (int r = 0; r < repeat; ++r) {
             HIP_OK(hipEventRecord(e0, nullptr));
-            vrx::runRaymarchingKernel(width, height, algo, camera, sinfo, scene, lit, fb, nullptr);
+            if (aa) vrx::runRaymarchingKernelAA(width, height, S, algo, camera, sinfo, scene, lit, fine, fb, nullptr, nullptr);
+            else vrx::runRaymarchingKernel(width, height, algo, camera, sinfo, scene, lit, fb, nullptr);
             HIP_OK(hipEventRecord(e1, nullptr));
             HIP_OK(hipEventSynchronize(e1));
             float ms = 0;
@@ -492,7 +523,9 @@ int main(int argc, char* argv[]) {
         // --add-light / --ambient: the frame written is the vr_shade_lights one -- the camera rays
         // of every pixel in 8x8-tile order (the order in which a frame's rays walk fastest), the
         // run's own light first and then the added ones, the words scattered back to their pixels
+        // (with --aa: the frame of S * width x S * height pixels, resolved into fb)
         if (lights_frame) {
+            const uint32_t lw = S * width, lh = S * height;
             std::vector<vr_lighting> lights(1, lit);
             for (const vr_ray& l : added_lights) {
                 vr_lighting k = vrx::defaultLighting();
@@ -501,14 +534,14 @@ int main(int argc, char* argv[]) {
                 k.use_shadows = shadows;
                 lights.push_back(k);
             }
-            const size_t n = (size_t)width * height;
+            const size_t n = (size_t)lw * lh;
             std::vector<uint32_t> px, py;
             px.reserve(n);
             py.reserve(n);
-            for (uint32_t ty = 0; ty < height; ty += 8)
-                for (uint32_t tx = 0; tx < width; tx += 8)
-                    for (uint32_t y = ty; y < std::min(ty + 8u, height); ++y)
-                        for (uint32_t x = tx; x < std::min(tx + 8u, width); ++x) {
+            for (uint32_t ty = 0; ty < lh; ty += 8)
+                for (uint32_t tx = 0; tx < lw; tx += 8)
+                    for (uint32_t y = ty; y < std::min(ty + 8u, lh); ++y)
+                        for (uint32_t x = tx; x < std::min(tx + 8u, lw); ++x) {
                             px.push_back(x);
                             py.push_back(y);
                         }
@@ -516,14 +549,15 @@ int main(int argc, char* argv[]) {
             HIP_OK(hipMalloc(&rays, n * sizeof(vr_ray)));
             const float t[3] = {sinfo.translationVector.x, sinfo.translationVector.y, sinfo.translationVector.z};
             std::vector<uint32_t> words(n), frame(n);
-            int rc = vr_camera_rays(device, &camera.raw(), width, height, px.data(), py.data(), n, 0, rays, 1, nullptr);
+            int rc = vr_camera_rays(device, &camera.raw(), lw, lh, px.data(), py.data(), n, 0, rays, 1, nullptr);
             if (rc == VR_OK)
                 rc = vr_shade_lights(scene.get(), (vr_algo)algo, lights.data(), lights.size(), has_ambient ? ambient : nullptr,
                                      t, sinfo.scale, rays, n, 1, words.data(), nullptr, 0, VR_TRACE_ORDER_AUTO, nullptr);
             (void)hipFree(rays);
             vrx::check(rc, "lights frame");
-            for (size_t i = 0; i < n; ++i) frame[(size_t)py[i] * width + px[i]] = words[i];
-            HIP_OK(hipMemcpy(fb, frame.data(), n * 4, hipMemcpyHostToDevice));
+            for (size_t i = 0; i < n; ++i) frame[(size_t)py[i] * lw + px[i]] = words[i];
+            HIP_OK(hipMemcpy(aa ? fine : fb, frame.data(), n * 4, hipMemcpyHostToDevice));
+            if (aa) vrx::resolve(fine, width, height, S, fb);
             std::printf("lights %zu ambient %.9g %.9g %.9g\n", lights.size(), has_ambient ? ambient[0] : 0.0f,
                         has_ambient ? ambient[1] : 0.0f, has_ambient ? ambient[2] : 0.0f);
             std::fflush(stdout);
@@ -543,6 +577,7 @@ int main(int argc, char* argv[]) {
         (void)hipHostFree(host);
         (void)hipFree(fb);
         (void)hipFree(rgb);
+        (void)hipFree(fine);
         if (rc != VR_OK) {
             std::cerr << "ERROR: Failed to write image to: " << out_path << " (" << vr_last_error() << ")" << std::endl;
             return 1;

@@ -1,5 +1,5 @@
 // vr_host.h -- what the host translation units of libvr.so share (vr_host.cpp, vr_scene.cpp,
-// vr_scene_io.cpp, vr_launch.cpp, vr_query_api.cpp).  Private: nothing declared here is exported.
+// vr_scene_io.cpp, vr_launch.cpp, vr_query_api.cpp, vr_aa_api.cpp).  Private: nothing declared here is exported.
 // (vr_staging.h, beside it: the staging buffers of the entry points that take host or device arrays.)
 #pragma once
 

@@ -274,5 +274,13 @@ struct LaneShape {
 LaneShape lane_shape();
 hipError_t launch_perm(const uint32_t* pcost, uint32_t LW, uint32_t rows, uint32_t gx, uint32_t gy, uint8_t* perm,
                        uint32_t* cost, hipStream_t stream);
+// (vr_resolve.hip: supersampled frames)
+// vr_resolve's kernel: the (S * W) x (S * rows) words at `fine` box-filtered to W x rows pixels,
+// S in {1, 2, 4, 8}, as packed words in out and/or RGB8 in rgb (either may be null, not both), from
+// one read of the fine frame.  resolve_vector_path: whether the launch takes its 16-byte loads (a
+// 16-byte aligned base and S = 4, S = 8 or S = 2 with an even W) or one-word loads.
+bool resolve_vector_path(const void* fine, uint32_t W, uint32_t S);
+hipError_t launch_resolve(const uint32_t* fine, uint32_t W, uint32_t rows, uint32_t S, uint32_t* out, uint8_t* rgb,
+                          hipStream_t stream);
 
 }  // namespace vr

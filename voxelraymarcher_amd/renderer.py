@@ -689,12 +689,22 @@ def _tile_order_pixels(width: int, height: int, device):
 
 
 def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, lights,
-                  width: int, height: int, ambient=None, stream=None) -> torch.Tensor:
+                  width: int, height: int, ambient=None, stream=None, samples: int = 1) -> torch.Tensor:
     """A width x height frame under several lights and an ambient term: shade_lights() of the
     frame's camera_rays(), as a (height, width) int32 CUDA tensor of 0x00RRGGBB words on the
     scene's device.  The rays are taken in 8 x 8-tile order (row-major rays measured 18-26 %
     slower, profiles/shade/README.md) and the words scattered back to their pixels.  With one light
-    and no ambient term it is the frame run_raymarching_kernel renders under that light."""
+    and no ambient term it is the frame run_raymarching_kernel renders under that light.
+    samples > 1 (2, 4 or 8 per axis): the (samples * width) x (samples * height) frame made the same
+    way -- its camera_rays in the 8 x 8-tile order of the fine frame -- and box-filtered by
+    resolve()."""
+    samples = int(samples)
+    if samples != 1:
+        if samples not in (2, 4, 8):
+            raise ValueError("samples must be 1, 2, 4 or 8")
+        fine = render_lights(scene, algorithm, camera, info, lights, samples * int(width), samples * int(height),
+                             ambient=ambient, stream=stream)
+        return resolve(fine, width, height, samples, stream=stream)
     device = torch.device(f"cuda:{scene.info()['device']}")
     stream = torch.cuda.current_stream(device) if stream is None else stream
     with torch.cuda.stream(stream):
@@ -704,6 +714,82 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
         frame = torch.empty((int(height), int(width)), dtype=torch.int32, device=device)
         frame[py.long(), px.long()] = words
     return frame
+
+
+def aa_fine_words(width: int, rows: int, samples: int) -> int:
+    """vr_aa_fine_words: the words of the fine frame behind `rows` rows of a frame `width` wide at
+    samples x samples samples per pixel; 0 for arguments render_aa() refuses."""
+    if not (0 <= int(width) < 1 << 32 and 0 <= int(rows) < 1 << 32 and 0 <= int(samples) < 1 << 32):
+        return 0
+    return int(lib().vr_aa_fine_words(int(width), int(rows), int(samples)))
+
+
+def _resolve_outputs(width: int, rows: int, rgb8, out, device):
+    """The outputs of resolve() and render_aa(): (words tensor or None, RGB8 tensor or None)."""
+    n = int(width) * int(rows)
+    rgb = None
+    if rgb8 is not False and rgb8 is not None:
+        rgb = torch.empty((int(rows), int(width), 3), dtype=torch.uint8, device=device) if rgb8 is True else rgb8
+        if not rgb.is_cuda or rgb.dtype != torch.uint8 or not rgb.is_contiguous() or rgb.numel() < 3 * n:
+            raise ValueError(f"rgb8 must be True or a contiguous CUDA uint8 tensor of >= {3 * n} bytes")
+    if out is None and rgb is None:
+        out = torch.empty((int(rows), int(width)), dtype=torch.int32, device=device)
+    if out is not None:
+        _require_u32(out, n)
+    return out, rgb
+
+
+def resolve(fine: torch.Tensor, width: int, rows: int, samples: int, rgb8=False, out: torch.Tensor | None = None,
+            stream=None):
+    """vr_resolve: box-filter the fine frame `fine` -- a contiguous CUDA int32/uint32 tensor of
+    (samples * width) x (samples * rows) packed words, row-major: a render, a render_lights frame,
+    an assembled multi-GPU frame -- to width x rows pixels: per channel the mean of a pixel's
+    samples x samples words, rounded half up; bits 24-31 of a fine word are dropped.  samples is 1,
+    2, 4 or 8 per axis.  Returns the words, a (rows, width) int32 tensor (or `out`, filled).
+    rgb8=True (or a uint8 tensor to fill): the pixels as RGB8 bytes, (rows, width, 3), R first, as
+    pack_rgb8 -- alone when `out` is None, else (out, rgb), both from one read of the fine frame.
+    Asynchronous on `stream` (default: the current stream); allocates only the outputs it returns."""
+    if not fine.is_cuda or fine.dtype not in (torch.int32, torch.uint32) or not fine.is_contiguous():
+        raise TypeError("fine must be a contiguous CUDA int32/uint32 tensor")
+    need = int(samples) * int(samples) * int(width) * int(rows)
+    if fine.numel() < need:
+        raise ValueError(f"fine must hold >= {need} words")
+    out, rgb = _resolve_outputs(width, rows, rgb8, out, fine.device)
+    with torch.cuda.device(fine.device):
+        check(lib().vr_resolve(_ptr(fine), int(width), int(rows), int(samples), None if out is None else _ptr(out),
+                               None if rgb is None else _ptr(rgb), _stream_ptr(stream)), "vr_resolve")
+    return rgb if out is None else (out if rgb is None else (out, rgb))
+
+
+def render_aa(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, lighting: _capi.VrLighting,
+              info: VoxelSceneInfo, width: int, height: int, samples: int, rows=None,
+              fine: torch.Tensor | None = None, out: torch.Tensor | None = None, rgb8=False, stream=None):
+    """vr_render_aa: the width x height frame at samples x samples (1, 2, 4 or 8 per axis) samples
+    per pixel -- run_raymarching_kernel's frame of (samples * width) x (samples * height), rendered
+    into `fine` and box-filtered as resolve() does it.  rows = (row_begin, row_end) renders and
+    resolves only those rows of the frame (default: all).  `fine`: a CUDA int32/uint32 tensor of
+    aa_fine_words(width, row_end - row_begin, samples) words that the caller keeps for the frame
+    loop (afterwards it holds the fine rows); allocated here when not given.  `out`, rgb8 and the
+    return value are resolve()'s.  An ordinary render launch: a repeated view learns and uses its
+    orders.  Asynchronous on `stream` (default: the current stream)."""
+    row_begin, row_end = (0, int(height)) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row_begin <= row_end:
+        raise ValueError("rows must be (row_begin, row_end) with 0 <= row_begin <= row_end")
+    nrows = row_end - row_begin
+    device = torch.device(f"cuda:{scene.info()['device']}")
+    words = aa_fine_words(width, nrows, samples)
+    if fine is None:
+        fine = torch.empty(max(words, 1), dtype=torch.int32, device=device)
+    if not fine.is_cuda or fine.dtype not in (torch.int32, torch.uint32) or not fine.is_contiguous():
+        raise TypeError("fine must be a contiguous CUDA int32/uint32 tensor")
+    out, rgb = _resolve_outputs(width, nrows, rgb8, out, device)
+    if nrows == 0 and row_end <= int(height):       # (an empty range does nothing; empty tensors have no address)
+        return rgb if out is None else (out if rgb is None else (out, rgb))
+    check(lib().vr_render_aa(scene.handle, int(algorithm), ctypes.byref(camera.raw), ctypes.byref(lighting),
+                             f3(info.translation), int(info.scale), int(width), int(height), int(samples), row_begin,
+                             row_end, _ptr(fine), fine.numel(), None if out is None else _ptr(out),
+                             None if rgb is None else _ptr(rgb), _stream_ptr(stream)), "vr_render_aa")
+    return rgb if out is None else (out if rgb is None else (out, rgb))
 
 
 def camera_rays(camera: Camera, width: int, height: int, px, py, device: int = 0, stream=None):
