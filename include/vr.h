@@ -430,6 +430,78 @@ int vr_shade_lights(const vr_scene* s, vr_algo algo,
                     uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
                     uint32_t order, void* stream);
 
+/* Voxel ambient occlusion: how open the face of a hit is at the hit point, from the eight voxels
+ * around the cell in front of the face.  ao[i] is ao(hits[i]), 0..255, VR_AO_OPEN (255) = open.
+ * It takes the records of vr_pick, vr_trace, vr_shade and vr_shade_lights, and records the caller
+ * made up: no record is rejected and any 64 bytes are safe.
+ *
+ * ao(h) is 255 unless h.status == VR_HIT_VOXEL and h.normal has exactly one component +1 or -1
+ * and the other two 0.  Otherwise, with all int32 arithmetic wrapping:
+ *   axes       a is the normal's axis; the tangent axes (u, w) are (1, 2), (2, 0), (0, 1) for
+ *              a = 0, 1, 2.
+ *   plane cell p = h.voxel + h.normal.
+ *   occupancy  o(du, dw) = 1 when world voxel p + du * e_u + dw * e_w is stored (vr_scene_lookup's
+ *              meaning: outside the frame, a null region, an absent cluster and an absent key are
+ *              empty), else 0.  The eight (du, dw) of {-1, 0, 1}^2 other than (0, 0) are read; p
+ *              itself never is.
+ *   corners    for (su, sw) in {-1, +1}^2, with s1 = o(su, 0), s2 = o(0, sw), c = o(su, sw):
+ *              L(su, sw) = (s1 & s2) ? 0 : 3 - (s1 + s2 + c).
+ *   position   for t in {u, w}: f_t = h.point[t] - (float)(int32)(h.voxel[t] - 64 * h.region[t]),
+ *              one fp32 subtraction; g = f_t * 256.0f (exact); q_t = 0 if !(g > 0) (NaN too), 256
+ *              if g >= 256, else (int)g (truncated).
+ *   sum        acc = (256 - q_u)(256 - q_w) L(-1,-1) + q_u (256 - q_w) L(+1,-1)
+ *                    + (256 - q_u) q_w L(-1,+1) + q_u q_w L(+1,+1)        (at most 3 * 65536)
+ *   result     ao = (acc * 255 + 98304) / 196608, an integer division.
+ * Applied to a colour word with a strength in 0..255 (vr_shade_lights_ao):
+ *   m = 255 - ((255 - ao) * strength + 127) / 255, and scale_rgb(word, m) replaces each of the
+ *   bytes R, G and B of word by (b * m + 127) / 255 and drops bits 24-31.  strength 0 gives
+ *   m = 255 and changes nothing; strength 255 gives m = ao.
+ *
+ * hits: n records, on the scene's device (16-byte aligned) when inputs_on_device != 0; ao: n
+ * words, on the device (4-byte aligned) when outputs_on_device != 0.  Host arrays are staged
+ * through device buffers the call allocates and frees; with everything on the device it
+ * allocates nothing.  The work (one small kernel, one lane per record) runs on `stream` and the
+ * call returns when ao[0..n) are written.  n == 0 returns VR_OK and does nothing.  As a trace, it
+ * is not a render launch: no ring slot, nothing learned or forgotten.
+ *
+ * VR_E_INVALID (nothing is written): s NULL; hits or ao NULL with n > 0; n >= 2^31; a misaligned
+ * device array; a stream that is capturing a HIP graph. */
+#define VR_AO_OPEN 255u
+int vr_occlusion(const vr_scene* s, const vr_hit* hits, size_t n, int inputs_on_device,
+                 uint32_t* ao, int outputs_on_device, void* stream);
+
+/* Where vr_shade_lights_ao applies the occlusion. */
+typedef enum {
+    VR_AO_AMBIENT = 0,   /* to the ambient term only: lit faces keep their light, the rest gains its corners */
+    VR_AO_ALL = 1        /* to the whole word */
+} vr_ao_apply;
+
+/* vr_shade_lights with voxel ambient occlusion, from the same single primary walk.  With
+ * m_i = the factor ao_strength (0..255) makes of ao(the hit of rays[i]) (vr_occlusion above):
+ *   VR_AO_AMBIENT  colors[i] is vr_shade_lights' sum with the ambient term T_a(i) replaced by
+ *                  scale_rgb(T_a(i), m_i) before summing;
+ *   VR_AO_ALL      colors[i] = scale_rgb(w_i, m_i), w_i vr_shade_lights' word.
+ * ao_out (may be NULL): ao_out[i] = ao(the hit of rays[i]) -- 255 for a miss and for a walk that
+ * never ends -- n words on the same side as colors (4-byte aligned on the device).  hits stays
+ * byte for byte vr_trace's record.  With ao_strength == 0 and ao_out == NULL the call is
+ * vr_shade_lights, word for word.  Every other argument is vr_shade_lights'.
+ *
+ * The occlusion pass reads the primary walk's records: when hits is NULL the call allocates a
+ * record buffer of its own (64 bytes per ray) beside vr_shade_lights' hit state and frees it
+ * before it returns.  One more small kernel runs on `stream`: after the primary kernel (AMBIENT)
+ * or after the last light (ALL).
+ *
+ * VR_E_INVALID (nothing is written): vr_shade_lights' cases; ao_strength > 255; an unknown
+ * ao_apply; a misaligned device ao_out. */
+int vr_shade_lights_ao(const vr_scene* s, vr_algo algo,
+                       const vr_lighting* lights, size_t n_lights,
+                       const float ambient[3] /* may be NULL */,
+                       const float translation[3], uint32_t scale,
+                       const vr_ray* rays, size_t n, int inputs_on_device,
+                       uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
+                       uint32_t order, void* stream,
+                       uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out /* may be NULL */);
+
 /* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
  * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
  * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the

@@ -251,6 +251,35 @@ inline std::vector<uint32_t> shadeLights(RayMarchAlgorithm algo, const VoxelScen
     return colors;
 }
 
+// vr_occlusion: voxel ambient occlusion of hit records (pick(), trace(), shade()'s, or made up): how
+// open each hit's face is at the hit point, 0..255 (VR_AO_OPEN = 255).  Host records in, host
+// values out; returns when they are written.
+inline std::vector<uint32_t> occlusion(const DeviceScene& scene, const std::vector<vr_hit>& hits, void* stream = nullptr) {
+    std::vector<uint32_t> ao(hits.size());
+    check(vr_occlusion(scene.get(), hits.data(), hits.size(), 0, ao.data(), 0, stream), "occlusion");
+    return ao;
+}
+
+// vr_shade_lights_ao: shadeLights() with the ambient term (VR_AO_AMBIENT) or the whole word
+// (VR_AO_ALL) scaled by the factor aoStrength (0..255) makes of each hit's occlusion; aoOut (or
+// nullptr) receives the occlusion values.
+inline std::vector<uint32_t> shadeLightsAo(RayMarchAlgorithm algo, const VoxelSceneInfo& info,
+                                           const std::vector<vr_lighting>& lights, const float* ambient,
+                                           const DeviceScene& scene, const std::vector<vr_ray>& rays, uint32_t aoStrength,
+                                           vr_ao_apply aoApply = VR_AO_AMBIENT, std::vector<uint32_t>* aoOut = nullptr,
+                                           std::vector<vr_hit>* hits = nullptr, vr_trace_order order = VR_TRACE_ORDER_AUTO,
+                                           void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> colors(rays.size());
+    if (hits) hits->assign(rays.size(), vr_hit{});
+    if (aoOut) aoOut->assign(rays.size(), VR_AO_OPEN);
+    check(vr_shade_lights_ao(scene.get(), (vr_algo)algo, lights.data(), lights.size(), ambient, t, info.scale, rays.data(),
+                             rays.size(), 0, colors.data(), hits ? hits->data() : nullptr, 0, (uint32_t)order, stream,
+                             aoStrength, (uint32_t)aoApply, aoOut ? aoOut->data() : nullptr),
+          "shadeLightsAo");
+    return colors;
+}
+
 // vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
 // frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
 inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,

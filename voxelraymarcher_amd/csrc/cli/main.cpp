@@ -34,6 +34,11 @@
 //                                 first, then the added ones, the terms summed per channel with a
 //                                 clamp at 255 -- and a line "lights <N> ambient <r> <g> <b>" is
 //                                 printed before "Wrote"; not with --gpus
+//                   [--ao STRENGTH] [--ao-all]  (voxel ambient occlusion, vr_shade_lights_ao: STRENGTH
+//                                 0..255 scales the ambient term -- with --ao-all the whole word --
+//                                 of the lights frame by each hit's occlusion; --ao selects the
+//                                 lights frame as --ambient does, and the "lights" line then ends
+//                                 in " ao <strength> <ambient|all>"; not with --gpus)
 //                   [--aa S]     (S = 1, 2, 4 or 8 samples per axis: output.png is the resolved frame --
 //                                 the (S * width) x (S * height) render box-filtered with round half
 //                                 up, vr_render_aa; with --add-light / --ambient the lights frame is
@@ -170,6 +175,8 @@ int main(int argc, char* argv[]) {
     std::vector<vr_ray> added_lights;        // --add-light DX,DY,DZ,R,G,B (repeatable): direction, colour
     bool has_ambient = false;                // --ambient R,G,B
     float ambient[3] = {0.0f, 0.0f, 0.0f};
+    bool has_ao = false, ao_all = false;     // --ao STRENGTH, --ao-all
+    uint32_t ao_strength = 0;
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -260,13 +267,23 @@ int main(int argc, char* argv[]) {
             }
             has_ambient = true;
         }
+        else if (a == "--ao") {
+            const char* v = next("--ao");
+            if (!is_integer(v) || std::atol(v) < 0 || std::atol(v) > 255) {
+                std::cerr << "--ao needs STRENGTH (0..255)" << std::endl;
+                std::exit(2);
+            }
+            ao_strength = (uint32_t)std::atol(v);
+            has_ao = true;
+        }
+        else if (a == "--ao-all") ao_all = true;
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
                          "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
                          "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]... [--add-light DX,DY,DZ,R,G,B]... "
-                         "[--ambient R,G,B] [--aa S]" << std::endl;
+                         "[--ambient R,G,B] [--ao STRENGTH] [--ao-all] [--aa S]" << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -300,9 +317,13 @@ int main(int argc, char* argv[]) {
         std::cerr << "ERROR: --paint changes this process's single-GPU scene: not with --gpus" << std::endl;
         return 2;
     }
-    const bool lights_frame = !added_lights.empty() || has_ambient;
+    if (ao_all && !has_ao) {
+        std::cerr << "ERROR: --ao-all needs --ao STRENGTH" << std::endl;
+        return 2;
+    }
+    const bool lights_frame = !added_lights.empty() || has_ambient || has_ao;
     if (lights_frame && multi) {             // (the frame is one device's vr_shade_lights call)
-        std::cerr << "ERROR: --add-light and --ambient shade a single-GPU frame: not with --gpus" << std::endl;
+        std::cerr << "ERROR: --add-light, --ambient and --ao shade a single-GPU frame: not with --gpus" << std::endl;
         return 2;
     }
     if (aa && multi) {                       // (a resolved frame dealt over several GPUs: a later change)
@@ -550,7 +571,11 @@ int main(int argc, char* argv[]) {
             const float t[3] = {sinfo.translationVector.x, sinfo.translationVector.y, sinfo.translationVector.z};
             std::vector<uint32_t> words(n), frame(n);
             int rc = vr_camera_rays(device, &camera.raw(), lw, lh, px.data(), py.data(), n, 0, rays, 1, nullptr);
-            if (rc == VR_OK)
+            if (rc == VR_OK && has_ao)
+                rc = vr_shade_lights_ao(scene.get(), (vr_algo)algo, lights.data(), lights.size(),
+                                        has_ambient ? ambient : nullptr, t, sinfo.scale, rays, n, 1, words.data(), nullptr, 0,
+                                        VR_TRACE_ORDER_AUTO, nullptr, ao_strength, ao_all ? VR_AO_ALL : VR_AO_AMBIENT, nullptr);
+            else if (rc == VR_OK)
                 rc = vr_shade_lights(scene.get(), (vr_algo)algo, lights.data(), lights.size(), has_ambient ? ambient : nullptr,
                                      t, sinfo.scale, rays, n, 1, words.data(), nullptr, 0, VR_TRACE_ORDER_AUTO, nullptr);
             (void)hipFree(rays);
@@ -558,8 +583,10 @@ int main(int argc, char* argv[]) {
             for (size_t i = 0; i < n; ++i) frame[(size_t)py[i] * lw + px[i]] = words[i];
             HIP_OK(hipMemcpy(aa ? fine : fb, frame.data(), n * 4, hipMemcpyHostToDevice));
             if (aa) vrx::resolve(fine, width, height, S, fb);
-            std::printf("lights %zu ambient %.9g %.9g %.9g\n", lights.size(), has_ambient ? ambient[0] : 0.0f,
+            std::printf("lights %zu ambient %.9g %.9g %.9g", lights.size(), has_ambient ? ambient[0] : 0.0f,
                         has_ambient ? ambient[1] : 0.0f, has_ambient ? ambient[2] : 0.0f);
+            if (has_ao) std::printf(" ao %u %s", ao_strength, ao_all ? "all" : "ambient");
+            std::printf("\n");
             std::fflush(stdout);
         }
         // writeResultingImageToDisk (Main.cu:165-174): RGB8 pack on the device,

@@ -1,42 +1,10 @@
 // vr_access.hip -- voxel access by coordinate: vr_scene_lookup's kernel and the three kernels of
 // vr_scene_paint.  One lane per query; everything rests on locate(), which finds
-// the value word of a world voxel in the live image of either store.
-#include "vr_device.h"
+// the value word of a world voxel in the live image of either store (vr_locate.h).
+#include "vr_locate.h"
 
 namespace vr {
 namespace {
-
-using F = Ctx<STORE_VCS, false, kTileBudget>;   // (for its static arithmetic: word_index, word_bit5)
-
-// The word that holds the colour of world voxel (x, y, z) -- an entry of vcs_vals, or the value
-// half of a cuckoo slot -- or null when the voxel is not stored: its 64^3 region outside the
-// frame, a null region, an absent cluster, an absent key.  Set membership in the voxel set
-// vr_scene_voxels returns: a world coordinate always has local coordinates in [0, 64), so none
-// of the walks' out-of-region lookups (vr_device.h lookup_aliased, wrapped keys) exists here.
-template <int STORE>
-__device__ __forceinline__ const uint32_t* locate(const KScene& s, int32_t x, int32_t y, int32_t z) {
-    // region = floor(c / 64), tested against the frame as Ctx::in_scene does (unsigned wrap:
-    // any int32 coordinate gives a region in [-2^25, 2^25), far from wrapping back into D <= 1024)
-    const uint32_t mc = (uint32_t)s.min_coord;
-    const uint32_t ux = (uint32_t)(x >> 6) - mc, uy = (uint32_t)(y >> 6) - mc, uz = (uint32_t)(z >> 6) - mc;
-    if (ux >= s.D || uy >= s.D || uz >= s.D) return nullptr;
-    const uint32_t r = s.region_slot[ux + uy * s.D + uz * s.D * s.D];
-    if (r == kNone) return nullptr;
-    const uint32_t lx = (uint32_t)x & 63u, ly = (uint32_t)y & 63u, lz = (uint32_t)z & 63u;
-    const uint32_t w = F::word_index(lx, ly, lz), bit = F::word_bit5(ly, lz) & 31u;
-    if (STORE == STORE_VCS) {
-        const uint2 m = s.vcs_mask[(size_t)r * 8192u + w];      // an absent cluster's words are {0, kNone}
-        if (!((m.x >> bit) & 1u)) return nullptr;
-        return s.vcs_vals + (m.y + __popc(m.x & ((1u << bit) - 1u)));
-    }
-    if (!((s.ht_filter[(size_t)r * kHashFilterWords + w] >> bit) & 1u)) return nullptr;
-    const uint32_t key = (lx << 20) | (ly << 10) | lz;          // generate3DPoint
-    const uint4 m = s.ht_meta[r];                                // {base, M, prime, offset}
-    const uint2* e = s.ht_slots + m.x + hash1(key, m.w) % m.y;
-    if (e->x != key) e = s.ht_slots + m.x + m.y + hash2(key, m.z) % m.y;
-    if (e->x != key) return nullptr;                             // (a filter bit without its key: never, by construction)
-    return &e->y;
-}
 
 template <int STORE>
 __global__ void lookup_kernel(KScene s, const int32_t* __restrict__ xyz, uint32_t n, uint32_t* __restrict__ rgb) {

@@ -238,6 +238,14 @@ hipError_t launch_paint_check(int store, const KScene& s, const int32_t* xyz, co
 // may run on the scene between the two.
 hipError_t launch_paint_apply(int store, const KScene& s, const int32_t* xyz, const uint32_t* rgb, uint32_t n,
                               hipStream_t stream);
+// (vr_occlusion.hip: voxel ambient occlusion)
+// vr_occlusion's kernel: ao[i] = the occlusion (0..255, 255 open) of the n vr_hit records at hits
+// (16-byte aligned device memory), one lane per record.  launch_occlusion_apply: the same value
+// per record, written to ao_out[i] when ao_out is not null, and colors[i] scaled per channel by
+// the factor `strength` (0..255) makes of it.
+hipError_t launch_occlusion(int store, const KScene& s, const void* hits, uint32_t n, uint32_t* ao, hipStream_t stream);
+hipError_t launch_occlusion_apply(int store, const KScene& s, const void* hits, uint32_t n, uint32_t strength,
+                                  uint32_t* colors, uint32_t* ao_out, hipStream_t stream);
 // (vr_util.hip, to launch_assemble_tiles)
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);

@@ -1,6 +1,6 @@
 // vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace, vr_shade,
-// vr_shade_lights and vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip, vr_shade.hip,
-// vr_lights.hip).  None is a render launch: no slot
+// vr_shade_lights, vr_shade_lights_ao, vr_occlusion and vr_camera_rays (their kernels: vr_query.hip,
+// vr_trace.hip, vr_shade.hip, vr_lights.hip, vr_occlusion.hip).  None is a render launch: no slot
 // lease, no view key, nothing the render path keeps per device (vr_launch.cpp) is touched.  Each
 // takes its arrays on the host or on the device (vr_staging.h), and in each every argument
 // check comes before any device work.
@@ -47,6 +47,101 @@ int finish(Staging& sg, hipError_t e, void* host, const void* dev, size_t bytes,
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return hip_fail(e, who);
     return VR_OK;
+}
+
+// What vr_shade_lights_ao adds to vr_shade_lights' arguments.
+struct AoArgs {
+    uint32_t strength, apply;
+    uint32_t* out;
+};
+
+// The body of vr_shade_lights (ao null) and vr_shade_lights_ao, under the name `who` in every
+// message.  The occlusion pass (vr_occlusion.hip launch_occlusion_apply) runs over the records of
+// the primary walk -- the caller's, or an internal buffer when hits is NULL -- straight after the
+// primary kernel, when colors holds the ambient term alone (VR_AO_AMBIENT), or after the last
+// light (VR_AO_ALL).  With strength 0 and no ao_out it does not run, no record buffer is made and
+// the call is vr_shade_lights'.
+int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights,
+                 const float ambient[3], const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
+                 int inputs_on_device, uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream,
+                 const AoArgs* ao) {
+    const std::string who(who_c);
+    if (!s) return fail(VR_E_INVALID, who + ": scene is NULL");
+    if (!translation) return fail(VR_E_INVALID, who + ": translation NULL");
+    if (n_lights && !lights) return fail(VR_E_INVALID, who + ": lights NULL");
+    if (n_lights > VR_MAX_LIGHTS) return fail(VR_E_INVALID, who + ": too many lights (VR_MAX_LIGHTS)");
+    if (n && (!rays || !colors)) return fail(VR_E_INVALID, who + ": rays/colors NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, who + ": too many rays");
+    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS)
+        return fail(VR_E_INVALID, who + ": unknown algorithm");
+    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
+        return fail(VR_E_INVALID, who + ": unknown order");
+    if (ao && ao->strength > 255u) return fail(VR_E_INVALID, who + ": ao_strength above 255");
+    if (ao && ao->apply != VR_AO_AMBIENT && ao->apply != VR_AO_ALL) return fail(VR_E_INVALID, who + ": unknown ao_apply");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
+        return fail(VR_E_INVALID, who + ": device rays must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)colors & 3u) != 0u)
+        return fail(VR_E_INVALID, who + ": device colors must be 4-byte aligned");
+    if (outputs_on_device && hits && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, who + ": device hits must be 16-byte aligned");
+    if (outputs_on_device && ao && ao->out && ((uintptr_t)ao->out & 3u) != 0u)
+        return fail(VR_E_INVALID, who + ": device ao_out must be 4-byte aligned");
+    // the trace's view for the primary walk (no camera, no light, no frame)
+    vr::KView v;
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
+    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
+    // AUTO is GIVEN, as vr_trace's (vr.h)
+    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
+    DeviceGuard dg(s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, who_c)) return rc;
+    Staging sg(st);           // (owns every buffer below: freed on every path, after the stream has drained)
+    const void* dr = inputs_on_device ? rays : sg.upload(rays, n * sizeof(vr_ray));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, (who + ": ray upload").c_str());
+    uint32_t* dc = outputs_on_device ? colors : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    void* dh = (outputs_on_device || !hits) ? hits : sg.make(n * sizeof(vr_hit));
+    // the occlusion pass reads the primary walk's records: the caller's, or a buffer of this call
+    const bool occlude = ao && (ao->strength != 0u || ao->out);
+    void* rec = dh;
+    if (occlude && !rec) rec = sg.make(n * sizeof(vr_hit));
+    uint32_t* da = nullptr;
+    if (occlude && ao->out) da = outputs_on_device ? ao->out : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, (who + ": output buffers").c_str());
+    // the per-ray hit state between the primary pass and the light passes (32 bytes per ray)
+    void* state = sg.make(n * 32u);
+    if (sg.err == hipErrorOutOfMemory) return fail(VR_E_NOMEM, who + ": hit state: " + std::string(hipGetErrorString(sg.err)));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, (who + ": hit state").c_str());
+    hipError_t e = hipSuccess;
+    const uint32_t* idx = nullptr;
+    if (coherent) {
+        void* scratch = nullptr;
+        e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &scratch, &idx);
+        sg.adopt(scratch);
+    }
+    if (e == hipSuccess)
+        e = vr::launch_lights_primary((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, ambient, state, dc,
+                                      rec, st);
+    if (occlude && ao->apply == VR_AO_AMBIENT && e == hipSuccess)     // (colors holds the ambient term alone)
+        e = vr::launch_occlusion_apply((int)s->store, vr::kscene(s), rec, (uint32_t)n, ao->strength, dc, da, st);
+    for (size_t k = 0; k < n_lights && e == hipSuccess; ++k) {
+        // light k as vr_shade takes it: the render's lighting block in the same view
+        vr::KView lv = v;
+        vr::view_lighting(lv, &lights[k]);
+        e = vr::launch_light_term((int)s->store, (int)algo, vr::kscene(s), lv, idx, (uint32_t)n, state, dc, st);
+    }
+    if (occlude && ao->apply == VR_AO_ALL && e == hipSuccess)
+        e = vr::launch_occlusion_apply((int)s->store, vr::kscene(s), rec, (uint32_t)n, ao->strength, dc, da, st);
+    if (e == hipSuccess && da && ao->out != da) {
+        sg.fetch(ao->out, da, n * sizeof(uint32_t));
+        e = sg.err;
+    }
+    if (e == hipSuccess && hits != dh) {        // (the records' way back; the colours': finish)
+        sg.fetch(hits, dh, n * sizeof(vr_hit));
+        e = sg.err;
+    }
+    return finish(sg, e, colors, dc, n * sizeof(uint32_t), who_c);
 }
 
 }  // namespace
@@ -189,64 +284,42 @@ int vr_shade(const vr_scene* s, vr_algo algo, const vr_lighting* lit, const floa
 int vr_shade_lights(const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights, const float ambient[3],
                     const float translation[3], uint32_t scale, const vr_ray* rays, size_t n, int inputs_on_device,
                     uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream) {
-    if (!s) return fail(VR_E_INVALID, "vr_shade_lights: scene is NULL");
-    if (!translation) return fail(VR_E_INVALID, "vr_shade_lights: translation NULL");
-    if (n_lights && !lights) return fail(VR_E_INVALID, "vr_shade_lights: lights NULL");
-    if (n_lights > VR_MAX_LIGHTS) return fail(VR_E_INVALID, "vr_shade_lights: too many lights (VR_MAX_LIGHTS)");
-    if (n && (!rays || !colors)) return fail(VR_E_INVALID, "vr_shade_lights: rays/colors NULL");
-    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_shade_lights: too many rays");
-    if (algo != VR_ALGO_ORIGINAL && algo != VR_ALGO_LONGESTAXIS)
-        return fail(VR_E_INVALID, "vr_shade_lights: unknown algorithm");
-    if (order != VR_TRACE_ORDER_AUTO && order != VR_TRACE_ORDER_GIVEN && order != VR_TRACE_ORDER_COHERENT)
-        return fail(VR_E_INVALID, "vr_shade_lights: unknown order");
+    return shade_lights("vr_shade_lights", s, algo, lights, n_lights, ambient, translation, scale, rays, n, inputs_on_device,
+                        colors, hits, outputs_on_device, order, stream, nullptr);
+}
+
+// vr_shade_lights with the ambient term, or the whole word, scaled by the hit's occlusion (vr.h).
+int vr_shade_lights_ao(const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights, const float ambient[3],
+                       const float translation[3], uint32_t scale, const vr_ray* rays, size_t n, int inputs_on_device,
+                       uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream,
+                       uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out) {
+    const AoArgs ao{ao_strength, ao_apply, ao_out};
+    return shade_lights("vr_shade_lights_ao", s, algo, lights, n_lights, ambient, translation, scale, rays, n,
+                        inputs_on_device, colors, hits, outputs_on_device, order, stream, &ao);
+}
+
+// How open the face of each hit is at the hit point (vr.h).
+int vr_occlusion(const vr_scene* s, const vr_hit* hits, size_t n, int inputs_on_device, uint32_t* ao, int outputs_on_device,
+                 void* stream) {
+    static_assert(VR_AO_OPEN == 255u, "VR_AO_OPEN: vr_occlusion_math.h kAoOpen");
+    if (!s) return fail(VR_E_INVALID, "vr_occlusion: scene is NULL");
+    if (n && (!hits || !ao)) return fail(VR_E_INVALID, "vr_occlusion: hits/ao NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_occlusion: too many records");
     if (n == 0) return VR_OK;
-    if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
-        return fail(VR_E_INVALID, "vr_shade_lights: device rays must be 16-byte aligned");
-    if (outputs_on_device && ((uintptr_t)colors & 3u) != 0u)
-        return fail(VR_E_INVALID, "vr_shade_lights: device colors must be 4-byte aligned");
-    if (outputs_on_device && hits && ((uintptr_t)hits & 15u) != 0u)
-        return fail(VR_E_INVALID, "vr_shade_lights: device hits must be 16-byte aligned");
-    // the trace's view for the primary walk (no camera, no light, no frame)
-    vr::KView v;
-    memset(&v, 0, sizeof v);
-    for (int i = 0; i < 3; ++i) v.translation[i] = translation[i];
-    v.scale_f = (float)scale;          // static_cast<float>(scale) (Ray.cuh:16)
-    // AUTO is GIVEN, as vr_trace's (vr.h)
-    const bool coherent = order == VR_TRACE_ORDER_COHERENT;
+    if (inputs_on_device && ((uintptr_t)hits & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_occlusion: device hits must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)ao & 3u) != 0u)
+        return fail(VR_E_INVALID, "vr_occlusion: device ao must be 4-byte aligned");
     DeviceGuard dg(s->device);
     const hipStream_t st = (hipStream_t)stream;
-    if (const int rc = vr::refuse_capture(st, "vr_shade_lights")) return rc;
-    Staging sg(st);           // (owns every buffer below: freed on every path, after the stream has drained)
-    const void* dr = inputs_on_device ? rays : sg.upload(rays, n * sizeof(vr_ray));
-    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: ray upload");
-    uint32_t* dc = outputs_on_device ? colors : (uint32_t*)sg.make(n * sizeof(uint32_t));
-    void* dh = (outputs_on_device || !hits) ? hits : sg.make(n * sizeof(vr_hit));
-    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: output buffers");
-    // the per-ray hit state between the primary pass and the light passes (32 bytes per ray)
-    void* state = sg.make(n * 32u);
-    if (sg.err == hipErrorOutOfMemory) return fail(VR_E_NOMEM, "vr_shade_lights: hit state: " + std::string(hipGetErrorString(sg.err)));
-    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_shade_lights: hit state");
-    hipError_t e = hipSuccess;
-    const uint32_t* idx = nullptr;
-    if (coherent) {
-        void* scratch = nullptr;
-        e = vr::trace_order(vr::kscene(s), v, dr, (uint32_t)n, st, &scratch, &idx);
-        sg.adopt(scratch);
-    }
-    if (e == hipSuccess)
-        e = vr::launch_lights_primary((int)s->store, (int)algo, vr::kscene(s), v, dr, idx, (uint32_t)n, ambient, state, dc,
-                                      dh, st);
-    for (size_t k = 0; k < n_lights && e == hipSuccess; ++k) {
-        // light k as vr_shade takes it: the render's lighting block in the same view
-        vr::KView lv = v;
-        vr::view_lighting(lv, &lights[k]);
-        e = vr::launch_light_term((int)s->store, (int)algo, vr::kscene(s), lv, idx, (uint32_t)n, state, dc, st);
-    }
-    if (e == hipSuccess && hits != dh) {        // (the records' way back; the colours': finish)
-        sg.fetch(hits, dh, n * sizeof(vr_hit));
-        e = sg.err;
-    }
-    return finish(sg, e, colors, dc, n * sizeof(uint32_t), "vr_shade_lights");
+    if (const int rc = vr::refuse_capture(st, "vr_occlusion")) return rc;
+    Staging sg(st);
+    const void* dh = inputs_on_device ? hits : sg.upload(hits, n * sizeof(vr_hit));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_occlusion: record upload");
+    uint32_t* da = outputs_on_device ? ao : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_occlusion: ao buffer");
+    const hipError_t e = vr::launch_occlusion((int)s->store, vr::kscene(s), dh, (uint32_t)n, da, st);
+    return finish(sg, e, ao, da, n * sizeof(uint32_t), "vr_occlusion");
 }
 
 // The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.

@@ -217,9 +217,15 @@ class DeviceScene:
         return shade(self, algorithm, info, lighting, rays, order=TraceOrder.AUTO if order is None else order,
                      hits=hits, stream=stream)
 
-    def shade_lights(self, algorithm, info, lights, rays, ambient=None, order=None, hits: bool = False, stream=None):
-        """vr_shade_lights with this scene: see shade_lights()."""
-        return shade_lights(self, algorithm, info, lights, rays, ambient=ambient, order=order, hits=hits, stream=stream)
+    def shade_lights(self, algorithm, info, lights, rays, ambient=None, order=None, hits: bool = False, stream=None,
+                     ao=None, ao_apply=None, return_ao: bool = False):
+        """vr_shade_lights (or, with ao=, vr_shade_lights_ao) with this scene: see shade_lights()."""
+        return shade_lights(self, algorithm, info, lights, rays, ambient=ambient, order=order, hits=hits, stream=stream,
+                            ao=ao, ao_apply=ao_apply, return_ao=return_ao)
+
+    def occlusion(self, hits, stream=None):
+        """vr_occlusion with this scene: see occlusion()."""
+        return occlusion(self, hits, stream=stream)
 
     def close(self) -> None:
         if self._h:
@@ -648,8 +654,43 @@ def shade(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo
     return (colors, recs) if hits else colors
 
 
+class AoApply(enum.IntEnum):
+    """vr_ao_apply: what shade_lights(ao=...) scales by the occlusion."""
+    AMBIENT = _capi.VR_AO_AMBIENT    # the ambient term only
+    ALL = _capi.VR_AO_ALL            # the whole word
+
+
+AO_OPEN = _capi.VR_AO_OPEN
+
+
+def occlusion(scene: DeviceScene, hits, stream=None):
+    """vr_occlusion: voxel ambient occlusion of hit records -- for each record how open its face is
+    at the hit point, 0..255 (AO_OPEN = 255), from the eight voxels around the cell in front of the
+    face (include/vr.h has the arithmetic).  Records of pick(), trace(), shade() and shade_lights(),
+    or made up: a record that is no VOXEL hit with a unit axis normal is open.  A numpy HIT_DTYPE
+    array gives a uint32 numpy array; an (n, 16) int32 CUDA tensor on the scene's device gives an
+    int32 CUDA tensor of shape (n,).  Runs on `stream` (default: the current stream) and returns
+    when the values are written; no render launch."""
+    dev = int(hasattr(hits, "is_cuda") and hits.is_cuda)
+    if dev:
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 16:
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        hits = hits.contiguous()
+        ao = torch.empty(hits.shape[0], dtype=torch.int32, device=hits.device)
+    else:
+        if not (isinstance(hits, np.ndarray) and hits.dtype == HIT_DTYPE):
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        hits = np.ascontiguousarray(hits).reshape(-1)
+        ao = np.zeros(hits.shape[0], dtype=np.uint32)
+    if hits.shape[0]:
+        check(lib().vr_occlusion(scene.handle, _ptr(hits), hits.shape[0], dev, _ptr(ao), dev, _stream_ptr(stream)),
+              "vr_occlusion")
+    return ao
+
+
 def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, lights, rays, ambient=None,
-                 order: TraceOrder | None = None, hits: bool = False, stream=None):
+                 order: TraceOrder | None = None, hits: bool = False, stream=None, ao=None, ao_apply=None,
+                 return_ao: bool = False):
     """vr_shade_lights: shade() under several lights and an ambient term, from one primary walk per
     ray.  `lights` is a sequence of VrLighting blocks (at most VR_MAX_LIGHTS, possibly empty), each
     taken exactly as shade() takes its one; `ambient` is three floats or None.  colours[i] is, per
@@ -657,7 +698,13 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     term of the hit's stored colour) -- independent of the order of the lights; a miss and a
     primary walk that never ends give 0.  Ray forms, output forms, `order` and hits=True are
     shade()'s.  Runs on `stream` (default: the current stream) and returns when the outputs are
-    written."""
+    written.
+    ao (a strength 0..255, or None): vr_shade_lights_ao -- the ambient term (ao_apply
+    AoApply.AMBIENT, the default) or the whole word (AoApply.ALL) scaled by the factor the strength
+    makes of the hit's occlusion(); return_ao=True appends the occlusion values (as occlusion()
+    returns them) to the result.  With ao=None the call is vr_shade_lights."""
+    if ao is None and (return_ao or ao_apply is not None):
+        raise ValueError("ao_apply and return_ao need ao= (a strength 0..255)")
     lights = list(lights)
     block = (_capi.VrLighting * max(len(lights), 1))(*lights)
     if ambient is not None and len(ambient) != 3:
@@ -669,11 +716,24 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     n = rays.shape[0]
     colors = torch.empty(n, dtype=torch.int32, device=rays.device) if dev else np.zeros(n, dtype=np.uint32)
     recs = _records(n, HIT_DTYPE, rays) if hits else None
-    if len(lights) > _capi.VR_MAX_LIGHTS or n:     # (the library refuses too many lights, with its message)
-        check(lib().vr_shade_lights(*args, _ptr(rays), n, dev, _ptr(colors), _ptr(recs) if hits else None, dev,
-                                    int(TraceOrder.AUTO if order is None else order), _stream_ptr(stream)),
-              "vr_shade_lights")
-    return (colors, recs) if hits else colors
+    tail = (_ptr(rays), n, dev, _ptr(colors), _ptr(recs) if hits else None, dev,
+            int(TraceOrder.AUTO if order is None else order), _stream_ptr(stream))
+    if ao is None:
+        if len(lights) > _capi.VR_MAX_LIGHTS or n:     # (the library refuses too many lights, with its message)
+            check(lib().vr_shade_lights(*args, *tail), "vr_shade_lights")
+        return (colors, recs) if hits else colors
+    strength, apply = int(ao), int(AoApply.AMBIENT if ao_apply is None else ao_apply)
+    if not 0 <= strength < 1 << 32 or not 0 <= apply < 1 << 32:
+        raise ValueError("ao must be a strength 0..255 and ao_apply an AoApply")
+    values = None
+    if return_ao:
+        values = torch.empty(n, dtype=torch.int32, device=rays.device) if dev else np.zeros(n, dtype=np.uint32)
+    # (the library refuses too many lights, a strength above 255 and an unknown mode, with its message)
+    if len(lights) > _capi.VR_MAX_LIGHTS or strength > 255 or apply not in (0, 1) or n:
+        check(lib().vr_shade_lights_ao(*args, *tail, strength, apply, _ptr(values) if return_ao else None),
+              "vr_shade_lights_ao")
+    out = (colors,) + ((recs,) if hits else ()) + ((values,) if return_ao else ())
+    return out if len(out) > 1 else colors
 
 
 def _tile_order_pixels(width: int, height: int, device):
@@ -689,7 +749,8 @@ def _tile_order_pixels(width: int, height: int, device):
 
 
 def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, lights,
-                  width: int, height: int, ambient=None, stream=None, samples: int = 1) -> torch.Tensor:
+                  width: int, height: int, ambient=None, stream=None, samples: int = 1, ao=None, ao_apply=None,
+                  return_ao: bool = False):
     """A width x height frame under several lights and an ambient term: shade_lights() of the
     frame's camera_rays(), as a (height, width) int32 CUDA tensor of 0x00RRGGBB words on the
     scene's device.  The rays are taken in 8 x 8-tile order (row-major rays measured 18-26 %
@@ -697,22 +758,33 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
     and no ambient term it is the frame run_raymarching_kernel renders under that light.
     samples > 1 (2, 4 or 8 per axis): the (samples * width) x (samples * height) frame made the same
     way -- its camera_rays in the 8 x 8-tile order of the fine frame -- and box-filtered by
-    resolve()."""
+    resolve().
+    ao, ao_apply: shade_lights()'s, for every ray of the frame (of the fine frame with samples > 1).
+    return_ao=True returns (frame, values): the occlusion values of the frame's pixels as a
+    (height, width) int32 CUDA tensor -- of the fine frame's, (samples * height, samples * width),
+    with samples > 1 (they are not filtered)."""
     samples = int(samples)
     if samples != 1:
         if samples not in (2, 4, 8):
             raise ValueError("samples must be 1, 2, 4 or 8")
         fine = render_lights(scene, algorithm, camera, info, lights, samples * int(width), samples * int(height),
-                             ambient=ambient, stream=stream)
+                             ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply, return_ao=return_ao)
+        if return_ao:
+            return resolve(fine[0], width, height, samples, stream=stream), fine[1]
         return resolve(fine, width, height, samples, stream=stream)
     device = torch.device(f"cuda:{scene.info()['device']}")
     stream = torch.cuda.current_stream(device) if stream is None else stream
     with torch.cuda.stream(stream):
         px, py = _tile_order_pixels(int(width), int(height), device)
         rays = camera_rays(camera, width, height, px, py, device=device.index, stream=stream)
-        words = shade_lights(scene, algorithm, info, lights, rays, ambient=ambient, stream=stream)
+        words = shade_lights(scene, algorithm, info, lights, rays, ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply,
+                             return_ao=return_ao)
         frame = torch.empty((int(height), int(width)), dtype=torch.int32, device=device)
-        frame[py.long(), px.long()] = words
+        frame[py.long(), px.long()] = words[0] if return_ao else words
+        if return_ao:
+            values = torch.empty((int(height), int(width)), dtype=torch.int32, device=device)
+            values[py.long(), px.long()] = words[1]
+            return frame, values
     return frame
 
 
