@@ -502,6 +502,91 @@ int vr_shade_lights_ao(const vr_scene* s, vr_algo algo,
                        uint32_t order, void* stream,
                        uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out /* may be NULL */);
 
+/* The mirror bounce of a ray at its hit: out[i] = bounce(rays[i], hits[i]), the ray that leaves the
+ * hit point along the incoming direction mirrored in the hit face.  It takes the records of
+ * vr_pick, vr_trace, vr_shade and vr_shade_lights, and records the caller made up: no record is
+ * rejected and any 64 bytes are safe.  No mirror test is applied: every VOXEL record bounces.
+ *
+ * bounce(ray, h) is defined when h.status == VR_HIT_VOXEL and h.normal has exactly one component +1
+ * or -1 and the other two 0 (vr_occlusion's condition); a is the normal's axis.  Then
+ *   origin[c]  = translation[c] + (((float)h.region[c] * 64.0f + h.point[c]) / (float)scale) for
+ *                each component c: int-to-float, multiply, add and divide, then the translation's
+ *                addition, each rounded to fp32 on its own in that order, the division correctly
+ *                rounded, no contraction -- the hit point back in world space;
+ *   direction  = ray.direction with the sign bit of component a flipped, the other two components
+ *                bitwise unchanged.  Nothing is normalised: the magnitude survives every depth.
+ *                For a direction without a zero component this is d - 2 (d . n) n to the bit; a
+ *                zero, infinite or NaN component on the axis has its sign flipped all the same.
+ *   reserved0 and reserved1 are 0.
+ * For every other record the six floats are the quiet NaN 0x7FC00000, as vr_camera_rays writes for
+ * a pixel outside the frame.  Such a ray is NOT harmless to trace: on the golden scene it gives
+ * VR_HIT_NEVER under three store/algorithm pairs and a VOXEL record under the hash table with the
+ * longest-axis walk.  A caller who traces the bounces must mask the results by the first
+ * record's status (vr_shade_lights_reflect below does the descent on the device and walks no such
+ * ray).  ray.origin is not read.
+ *
+ * Runs on `device` (no scene is needed) as one small kernel on `stream`, one lane per record, with
+ * 16-byte loads and stores.  rays and hits are both host arrays, or both on the device (16-byte
+ * aligned) when inputs_on_device != 0; out is on the device (16-byte aligned) when
+ * outputs_on_device != 0; host arrays are staged as vr_camera_rays stages them.  Returns when
+ * out[0..n) are written.  n == 0 returns VR_OK.
+ *
+ * VR_E_INVALID (nothing is written): translation NULL; rays, hits or out NULL with n > 0;
+ * n >= 2^31; device outside 0..63 or not present; a misaligned device array; a stream that is
+ * capturing a HIP graph. */
+int vr_bounce_rays(int device, const float translation[3], uint32_t scale,
+                   const vr_ray* rays, const vr_hit* hits, size_t n, int inputs_on_device,
+                   vr_ray* out, int outputs_on_device, void* stream);
+
+/* vr_shade_lights_ao with mirror reflections, the whole descent on the device: no record leaves
+ * it and no ray that does not reflect is walked again.
+ *
+ * With B = bounces (at most VR_MAX_BOUNCES) and k = reflectivity (0..255), ray^0_i = rays[i] and
+ * for depth j = 0..B:
+ *   W^j_i     the word vr_shade_lights_ao writes for ray^j_i under the same lights, ambient,
+ *             ao_strength and ao_apply, and H^j_i its record;
+ *   refl^j_i  H^j_i.status == VR_HIT_VOXEL and (H^j_i.color & mirror_mask) == mirror_value and
+ *             (j == 0 or refl^(j-1)_i);
+ *   ray^(j+1)_i = bounce(ray^j_i, H^j_i) (vr_bounce_rays above) where refl^j_i and j < B.
+ * Folded from the back: C^B_i = W^B_i, and for j = B - 1..0
+ *   C^j_i = refl^j_i ? mix(W^j_i, C^(j+1)_i, k) : W^j_i,        colors[i] = C^0_i,
+ * where mix(a, b, k) replaces each of the bytes R, G and B by (A * (255 - k) + B * k + 127) / 255,
+ * an integer division, and drops bits 24-31: k = 0 gives a and k = 255 gives b.  A bounce that
+ * misses, or whose walk never ends, contributes W = 0: a mirror shows the black background the
+ * renderer writes there.
+ *
+ * mirror_mask = 0 and mirror_value = 0: every voxel reflects.  A material bit (mask 1, value 1) or
+ * a key colour (mask 0xFFFFFF) selects the mirror voxels by their stored colour; vr_scene_paint
+ * paints them.  hits and ao_out belong to depth 0: hits[i] stays byte for byte vr_trace's record for
+ * rays[i].  order applies to depth 0; deeper depths run in the order of their lists, and no word
+ * depends on either.  With reflectivity == 0 or bounces == 0 the call is vr_shade_lights_ao, word
+ * for word: no extra kernel, allocation or readback.  Every other argument is vr_shade_lights_ao's.
+ *
+ * Per depth j >= 1 the call runs one small kernel that makes the bounce rays and the compact list
+ * of the rays that reflected, reads the list's 4-byte count back on `stream` (a wait for the
+ * stream per depth; a count of 0 ends the descent), runs vr_shade_lights_ao's kernels over the list
+ * alone -- the occlusion kernel, where ao_strength != 0, over all n records -- and at the end one
+ * small fold kernel per depth reached.  Beside vr_shade_lights_ao's buffers it allocates on the
+ * scene's device, in one allocation, and frees before it returns on every path: one ray buffer
+ * (two when bounces > 1; 32 bytes per ray each), per depth asked for a colour buffer and a list (4
+ * bytes per ray each), the counts, and a record buffer (64 bytes per ray) when ao_strength != 0.
+ * A failure there is VR_E_NOMEM or VR_E_HIP.  Not a render launch: no ring slot, nothing learned
+ * or forgotten.
+ *
+ * VR_E_INVALID (nothing is written; every check comes before any device work): vr_shade_lights_ao's
+ * cases; reflectivity > 255; bounces > VR_MAX_BOUNCES; mirror_value with a bit outside mirror_mask
+ * (it could never match). */
+#define VR_MAX_BOUNCES 4u
+int vr_shade_lights_reflect(const vr_scene* s, vr_algo algo,
+                            const vr_lighting* lights, size_t n_lights,
+                            const float ambient[3] /* may be NULL */,
+                            const float translation[3], uint32_t scale,
+                            const vr_ray* rays, size_t n, int inputs_on_device,
+                            uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
+                            uint32_t order, void* stream,
+                            uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out /* may be NULL */,
+                            uint32_t reflectivity, uint32_t bounces, uint32_t mirror_mask, uint32_t mirror_value);
+
 /* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
  * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
  * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the

@@ -280,6 +280,42 @@ inline std::vector<uint32_t> shadeLightsAo(RayMarchAlgorithm algo, const VoxelSc
     return colors;
 }
 
+// vr_bounce_rays: the mirror bounce of rays[i] at the hit record hits[i] (origin the hit point in
+// world units, direction the incoming one with the sign of the normal's axis flipped); an all-NaN
+// ray for a record that is no VOXEL hit -- mask what you trace by the records' status.
+inline std::vector<vr_ray> bounceRays(const VoxelSceneInfo& info, const std::vector<vr_ray>& rays,
+                                      const std::vector<vr_hit>& hits, int device = 0, void* stream = nullptr) {
+    if (rays.size() != hits.size()) throw Error(VR_E_INVALID, "bounceRays: rays and hits lengths differ");
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<vr_ray> out(rays.size());
+    check(vr_bounce_rays(device, t, info.scale, rays.data(), hits.data(), rays.size(), 0, out.data(), 0, stream), "bounceRays");
+    return out;
+}
+
+// vr_shade_lights_reflect: shadeLightsAo() (aoStrength 0: shadeLights()) with mirror reflections --
+// rays whose hit voxel has (stored colour & mirrorMask) == mirrorValue bounce up to `bounces` times
+// (at most VR_MAX_BOUNCES), every depth shaded as the first, and the words are blended from the back
+// by reflectivity (0..255).  hits and aoOut are the first hit's.  The descent stays on the device.
+inline std::vector<uint32_t> shadeLightsReflect(RayMarchAlgorithm algo, const VoxelSceneInfo& info,
+                                                const std::vector<vr_lighting>& lights, const float* ambient,
+                                                const DeviceScene& scene, const std::vector<vr_ray>& rays,
+                                                uint32_t reflectivity, uint32_t bounces = 1, uint32_t mirrorMask = 0,
+                                                uint32_t mirrorValue = 0, uint32_t aoStrength = 0,
+                                                vr_ao_apply aoApply = VR_AO_AMBIENT, std::vector<uint32_t>* aoOut = nullptr,
+                                                std::vector<vr_hit>* hits = nullptr,
+                                                vr_trace_order order = VR_TRACE_ORDER_AUTO, void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> colors(rays.size());
+    if (hits) hits->assign(rays.size(), vr_hit{});
+    if (aoOut) aoOut->assign(rays.size(), VR_AO_OPEN);
+    check(vr_shade_lights_reflect(scene.get(), (vr_algo)algo, lights.data(), lights.size(), ambient, t, info.scale,
+                                  rays.data(), rays.size(), 0, colors.data(), hits ? hits->data() : nullptr, 0,
+                                  (uint32_t)order, stream, aoStrength, (uint32_t)aoApply, aoOut ? aoOut->data() : nullptr,
+                                  reflectivity, bounces, mirrorMask, mirrorValue),
+          "shadeLightsReflect");
+    return colors;
+}
+
 // vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
 // frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
 inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,

@@ -84,6 +84,8 @@ VR_MAX_LIGHTS = 64
 VR_AO_OPEN = 255
 VR_AO_AMBIENT, VR_AO_ALL = 0, 1
 
+VR_MAX_BOUNCES = 4
+
 
 class VrError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str):
@@ -149,6 +151,11 @@ SIGNATURES = {
     "vr_shade_lights_ao": (c_int, [c_void_p, c_int, POINTER(VrLighting), c_size_t, POINTER(c_float), POINTER(c_float),
                                    c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_uint32, c_void_p,
                                    c_uint32, c_uint32, c_void_p]),
+    "vr_bounce_rays": (c_int, [c_int, POINTER(c_float), c_uint32, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                               c_void_p]),
+    "vr_shade_lights_reflect": (c_int, [c_void_p, c_int, POINTER(VrLighting), c_size_t, POINTER(c_float), POINTER(c_float),
+                                        c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_uint32, c_void_p,
+                                        c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32]),
     "vr_camera_rays": (c_int, [c_int, POINTER(VrCamera), c_uint32, c_uint32, c_void_p, c_void_p, c_size_t, c_int,
                                c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
@@ -201,6 +208,6 @@ __all__ = ["lib", "check", "VrCamera", "VrLighting", "VrRenderOpts", "VR_RENDER_
            "VR_SCHEDULE_HEAVIEST_FIRST", "VR_OCCUPANCY_AUTO", "VR_OCCUPANCY_LONE", "VR_OCCUPANCY_IN_FLIGHT",
            "VrSceneInfo", "VrSynthParams", "VrHit", "VR_HIT_MISS",
            "VR_HIT_VOXEL", "VR_HIT_NEVER", "VR_HIT_OUTSIDE", "VrRay", "VR_TRACE_ORDER_AUTO",
-           "VR_TRACE_ORDER_GIVEN", "VR_TRACE_ORDER_COHERENT", "VR_MAX_LIGHTS", "VR_AO_OPEN", "VR_AO_AMBIENT", "VR_AO_ALL", "VrError", "SIGNATURES",
+           "VR_TRACE_ORDER_GIVEN", "VR_TRACE_ORDER_COHERENT", "VR_MAX_LIGHTS", "VR_AO_OPEN", "VR_AO_AMBIENT", "VR_AO_ALL", "VR_MAX_BOUNCES", "VrError", "SIGNATURES",
            "VR_STORE_VCS", "VR_STORE_HASHTABLE", "VR_ALGO_LONGESTAXIS", "VR_ALGO_ORIGINAL", "f3", "LIB_PATH",
            "c_uint8"]

@@ -39,6 +39,13 @@
 //                                 of the lights frame by each hit's occlusion; --ao selects the
 //                                 lights frame as --ambient does, and the "lights" line then ends
 //                                 in " ao <strength> <ambient|all>"; not with --gpus)
+//                   [--reflect K] [--bounces B] [--mirror RRGGBB]  (mirror reflections,
+//                                 vr_shade_lights_reflect: K 0..255 blends up to B (default 1, at most 4)
+//                                 bounces into the lights frame's words; --mirror makes only voxels
+//                                 of that stored colour (hex) mirrors, the default is every voxel;
+//                                 --reflect selects the lights frame as --ambient does and works with
+//                                 --add-light, --ambient, --ao and --aa; the "lights" line then ends in
+//                                 " reflect <K> bounces <B> mirror <every|rrggbb>"; not with --gpus)
 //                   [--aa S]     (S = 1, 2, 4 or 8 samples per axis: output.png is the resolved frame --
 //                                 the (S * width) x (S * height) render box-filtered with round half
 //                                 up, vr_render_aa; with --add-light / --ambient the lights frame is
@@ -177,6 +184,8 @@ int main(int argc, char* argv[]) {
     float ambient[3] = {0.0f, 0.0f, 0.0f};
     bool has_ao = false, ao_all = false;     // --ao STRENGTH, --ao-all
     uint32_t ao_strength = 0;
+    bool has_reflect = false, has_bounces = false, has_mirror = false;     // --reflect K, --bounces B, --mirror RRGGBB
+    uint32_t reflect_k = 0, bounces = 1, mirror_rgb = 0;
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -277,13 +286,42 @@ int main(int argc, char* argv[]) {
             has_ao = true;
         }
         else if (a == "--ao-all") ao_all = true;
+        else if (a == "--reflect") {
+            const char* v = next("--reflect");
+            if (!is_integer(v) || std::atol(v) < 0 || std::atol(v) > 255) {
+                std::cerr << "--reflect needs K (0..255)" << std::endl;
+                std::exit(2);
+            }
+            reflect_k = (uint32_t)std::atol(v);
+            has_reflect = true;
+        }
+        else if (a == "--bounces") {
+            const char* v = next("--bounces");
+            if (!is_integer(v) || std::atol(v) < 0 || std::atol(v) > (long)VR_MAX_BOUNCES) {
+                std::cerr << "--bounces needs B (0.." << VR_MAX_BOUNCES << ")" << std::endl;
+                std::exit(2);
+            }
+            bounces = (uint32_t)std::atol(v);
+            has_bounces = true;
+        }
+        else if (a == "--mirror") {
+            const char* v = next("--mirror");
+            char* end = nullptr;
+            const unsigned long c = std::strtoul(v, &end, 16);
+            if (*v == '\0' || *end != '\0' || std::strlen(v) > 6) {
+                std::cerr << "--mirror needs RRGGBB (a stored colour, hex)" << std::endl;
+                std::exit(2);
+            }
+            mirror_rgb = (uint32_t)c;
+            has_mirror = true;
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
                          "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
                          "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]... [--add-light DX,DY,DZ,R,G,B]... "
-                         "[--ambient R,G,B] [--ao STRENGTH] [--ao-all] [--aa S]" << std::endl;
+                         "[--ambient R,G,B] [--ao STRENGTH] [--ao-all] [--reflect K] [--bounces B] [--mirror RRGGBB] [--aa S]" << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -321,9 +359,13 @@ int main(int argc, char* argv[]) {
         std::cerr << "ERROR: --ao-all needs --ao STRENGTH" << std::endl;
         return 2;
     }
-    const bool lights_frame = !added_lights.empty() || has_ambient || has_ao;
+    if ((has_bounces || has_mirror) && !has_reflect) {
+        std::cerr << "ERROR: --bounces and --mirror need --reflect K" << std::endl;
+        return 2;
+    }
+    const bool lights_frame = !added_lights.empty() || has_ambient || has_ao || has_reflect;
     if (lights_frame && multi) {             // (the frame is one device's vr_shade_lights call)
-        std::cerr << "ERROR: --add-light, --ambient and --ao shade a single-GPU frame: not with --gpus" << std::endl;
+        std::cerr << "ERROR: --add-light, --ambient, --ao and --reflect shade a single-GPU frame: not with --gpus" << std::endl;
         return 2;
     }
     if (aa && multi) {                       // (a resolved frame dealt over several GPUs: a later change)
@@ -571,7 +613,13 @@ int main(int argc, char* argv[]) {
             const float t[3] = {sinfo.translationVector.x, sinfo.translationVector.y, sinfo.translationVector.z};
             std::vector<uint32_t> words(n), frame(n);
             int rc = vr_camera_rays(device, &camera.raw(), lw, lh, px.data(), py.data(), n, 0, rays, 1, nullptr);
-            if (rc == VR_OK && has_ao)
+            if (rc == VR_OK && has_reflect)
+                rc = vr_shade_lights_reflect(scene.get(), (vr_algo)algo, lights.data(), lights.size(),
+                                             has_ambient ? ambient : nullptr, t, sinfo.scale, rays, n, 1, words.data(), nullptr,
+                                             0, VR_TRACE_ORDER_AUTO, nullptr, has_ao ? ao_strength : 0u,
+                                             ao_all ? VR_AO_ALL : VR_AO_AMBIENT, nullptr, reflect_k, bounces,
+                                             has_mirror ? 0xFFFFFFu : 0u, has_mirror ? mirror_rgb : 0u);
+            else if (rc == VR_OK && has_ao)
                 rc = vr_shade_lights_ao(scene.get(), (vr_algo)algo, lights.data(), lights.size(),
                                         has_ambient ? ambient : nullptr, t, sinfo.scale, rays, n, 1, words.data(), nullptr, 0,
                                         VR_TRACE_ORDER_AUTO, nullptr, ao_strength, ao_all ? VR_AO_ALL : VR_AO_AMBIENT, nullptr);
@@ -586,6 +634,8 @@ int main(int argc, char* argv[]) {
             std::printf("lights %zu ambient %.9g %.9g %.9g", lights.size(), has_ambient ? ambient[0] : 0.0f,
                         has_ambient ? ambient[1] : 0.0f, has_ambient ? ambient[2] : 0.0f);
             if (has_ao) std::printf(" ao %u %s", ao_strength, ao_all ? "all" : "ambient");
+            if (has_reflect && has_mirror) std::printf(" reflect %u bounces %u mirror %06x", reflect_k, bounces, mirror_rgb);
+            else if (has_reflect) std::printf(" reflect %u bounces %u mirror every", reflect_k, bounces);
             std::printf("\n");
             std::fflush(stdout);
         }

@@ -246,6 +246,23 @@ hipError_t launch_paint_apply(int store, const KScene& s, const int32_t* xyz, co
 hipError_t launch_occlusion(int store, const KScene& s, const void* hits, uint32_t n, uint32_t* ao, hipStream_t stream);
 hipError_t launch_occlusion_apply(int store, const KScene& s, const void* hits, uint32_t n, uint32_t strength,
                                   uint32_t* colors, uint32_t* ao_out, hipStream_t stream);
+// (vr_reflect.hip: mirror reflections)
+// vr_bounce_rays' kernel: out[i] = the bounce of rays[i] at hits[i] (vr_reflect_math.h) for n
+// records, one lane per record; rays, hits and out are 16-byte aligned device memory, scale_f is
+// (float)scale.
+hipError_t launch_bounce_rays(const void* rays, const void* hits, uint32_t n, const float translation[3], float scale_f,
+                              void* out, hipStream_t stream);
+// One depth's descent of vr_shade_lights_reflect, after launch_lights_primary on the same stream:
+// for each of the n_prev rays r = prev[i] (prev null: r = i) whose hit state says VOXEL and whose
+// stored colour has (col & mask) == value, rays_out[r] = the bounce of rays_in[r] at that hit, and
+// r is appended to list (n_prev words) with *count (zeroed by the caller) counting the entries.
+// rays_in and rays_out are different buffers of vr_ray records indexed by ray number.
+hipError_t launch_bounce_compact(const void* state, const void* rays_in, const uint32_t* prev, uint32_t n_prev,
+                                 uint32_t mask, uint32_t value, const float translation[3], float scale_f, void* rays_out,
+                                 uint32_t* list, uint32_t* count, hipStream_t stream);
+// shallow[r] = mix_rgb(shallow[r], deep[r], k) for the n rays r of list (k in 0..255).
+hipError_t launch_fold(const uint32_t* list, uint32_t n, uint32_t* shallow, const uint32_t* deep, uint32_t k,
+                       hipStream_t stream);
 // (vr_util.hip, to launch_assemble_tiles)
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);

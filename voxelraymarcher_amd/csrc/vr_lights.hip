@@ -7,18 +7,13 @@
 #include "vr_walk.h"
 
 #include "vr_lights_math.h"
+#include "vr_lights_state.h"
 
 namespace vr {
 namespace {
 
-// The per-ray hit state between the two kernels: what light_and_shadow (vr_walk.h) reads of a
-// Hit, 32 bytes as two 16-byte words --
-//   a = {col, nc | flags, so.x, so.y}     b = {so.z, region.x, region.y, region.z}
-// Hit::nc is bits(+-1.0f) | axis: its bits 2-22 are 0, and the flags sit there: kStLongest
-// (Hit::longest), kStHit (a primary VOXEL hit: the light passes run) and kStNever (the primary
-// walk never ends; kept apart from a miss for a reader of the buffer, the light passes skip
-// both).  A ray without a hit writes {0, flags, 0, 0} and a zero `b`, which is never read.
-constexpr uint32_t kStLongest = 4u, kStHit = 8u, kStNever = 16u, kStFlags = kStLongest | kStHit | kStNever;
+// (The per-ray hit state between the two kernels, 32 bytes as two 16-byte words, and its flags
+// kStLongest, kStHit and kStNever: vr_lights_state.h.)
 
 // Pass 1: ray r = idx ? idx[i] : i, loaded and walked as shade_rays_kernel (vr_shade.hip) does it
 // -- the exact walker, every walk run to its end, a walk that never finishes detected.  Writes

@@ -1,6 +1,7 @@
 // vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace, vr_shade,
-// vr_shade_lights, vr_shade_lights_ao, vr_occlusion and vr_camera_rays (their kernels: vr_query.hip,
-// vr_trace.hip, vr_shade.hip, vr_lights.hip, vr_occlusion.hip).  None is a render launch: no slot
+// vr_shade_lights, vr_shade_lights_ao, vr_shade_lights_reflect, vr_occlusion, vr_bounce_rays and
+// vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip, vr_shade.hip, vr_lights.hip,
+// vr_occlusion.hip, vr_reflect.hip).  None is a render launch: no slot
 // lease, no view key, nothing the render path keeps per device (vr_launch.cpp) is touched.  Each
 // takes its arrays on the host or on the device (vr_staging.h), and in each every argument
 // check comes before any device work.
@@ -55,7 +56,87 @@ struct AoArgs {
     uint32_t* out;
 };
 
-// The body of vr_shade_lights (ao null) and vr_shade_lights_ao, under the name `who` in every
+// What vr_shade_lights_reflect adds to vr_shade_lights_ao's arguments.
+struct ReflectArgs {
+    uint32_t reflectivity, bounces, mask, value;
+};
+
+// One light pass per light over the rays of idx (null: all n), as vr_shade takes each light: the
+// render's lighting block in the primary walk's view.
+hipError_t light_terms(const vr_scene* s, vr_algo algo, const vr::KView& v, const vr_lighting* lights, size_t n_lights,
+                       const uint32_t* idx, uint32_t n, const void* state, uint32_t* colors, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < n_lights && e == hipSuccess; ++k) {
+        vr::KView lv = v;
+        vr::view_lighting(lv, &lights[k]);
+        e = vr::launch_light_term((int)s->store, (int)algo, vr::kscene(s), lv, idx, n, state, colors, st);
+    }
+    return e;
+}
+
+// The depths below the first of vr_shade_lights_reflect, after depth 0's kernels on `st`: state holds
+// depth 0's hit state and colors0 its words W^0.  Per depth j >= 1 one bounce-and-compact pass
+// (vr_reflect.hip) makes ray^j and the list of the rays that reflected at depth j - 1, the list's
+// count comes back to the host (4 bytes, a wait for the stream: a count of 0 ends the descent),
+// and vr_lights.hip's launches run over the list as they ran over all rays at depth 0, into a
+// colour buffer of the depth.  The occlusion pass takes no list: it runs over all n records of a
+// record buffer of this call, in which only the list's rays hold this depth's records -- whatever
+// bytes the others hold are safe to read (vr_occlusion.hip) and their words are never read again.
+// Then the folds, deepest first.  All scratch is one allocation of sg's, cut into 256-byte aligned
+// parts -- the counts, the ray buffer(s), the record buffer, a list and a colour buffer per depth
+// asked for -- so the descent costs one hipMalloc and one hipFree whatever its depth (each costs
+// more than a depth's small kernels); it is freed on every path.
+hipError_t reflect_descend(Staging& sg, const vr_scene* s, vr_algo algo, const vr::KView& v, const vr_lighting* lights,
+                           size_t n_lights, const float* ambient, const AoArgs* ao, const ReflectArgs& rf, const void* rays0,
+                           uint32_t n, void* state, uint32_t* colors0, hipStream_t st) {
+    const bool occlude = ao && ao->strength != 0u;       // (ao_out belongs to depth 0)
+    const vr::KScene ks = vr::kscene(s);
+    const auto part = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
+    const size_t counts_b = part(VR_MAX_BOUNCES * sizeof(uint32_t)), rays_b = part((size_t)n * sizeof(vr_ray)),
+                 rec_b = occlude ? part((size_t)n * sizeof(vr_hit)) : 0u, words_b = part((size_t)n * sizeof(uint32_t));
+    const size_t n_raybufs = rf.bounces > 1u ? 2u : 1u;
+    char* base = (char*)sg.make(counts_b + n_raybufs * rays_b + rec_b + 2u * rf.bounces * words_b);
+    if (sg.err != hipSuccess) return sg.err;
+    uint32_t* counts = (uint32_t*)base;
+    void* raybuf[2] = {base + counts_b, n_raybufs > 1u ? base + counts_b + rays_b : nullptr};
+    void* rec = occlude ? base + counts_b + n_raybufs * rays_b : nullptr;
+    char* per_depth = base + counts_b + n_raybufs * rays_b + rec_b;      // depth j: its list, then its colours
+    hipError_t e = hipMemsetAsync(counts, 0, VR_MAX_BOUNCES * sizeof(uint32_t), st);
+    uint32_t* col[VR_MAX_BOUNCES + 1] = {colors0};
+    const uint32_t* list[VR_MAX_BOUNCES + 1] = {nullptr};
+    uint32_t cnt[VR_MAX_BOUNCES + 1] = {n};
+    const void* rays_prev = rays0;
+    uint32_t depth = 0;
+    for (uint32_t j = 1; j <= rf.bounces && e == hipSuccess; ++j) {
+        uint32_t* lj = (uint32_t*)(per_depth + 2u * (j - 1u) * words_b);
+        col[j] = (uint32_t*)(per_depth + (2u * (j - 1u) + 1u) * words_b);
+        void* rays_j = raybuf[(j - 1u) & 1u];
+        e = vr::launch_bounce_compact(state, rays_prev, list[j - 1], cnt[j - 1], rf.mask, rf.value, v.translation, v.scale_f,
+                                      rays_j, lj, counts + (j - 1u), st);
+        uint32_t c = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&c, counts + (j - 1u), sizeof c, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess || c == 0u) break;
+        if (c > cnt[j - 1]) return hipErrorUnknown;     // (cannot happen: a list never grows)
+        list[j] = lj;
+        cnt[j] = c;
+        depth = j;
+        e = vr::launch_lights_primary((int)s->store, (int)algo, ks, v, rays_j, lj, c, ambient, state, col[j], rec, st);
+        if (occlude && ao->apply == VR_AO_AMBIENT && e == hipSuccess)
+            e = vr::launch_occlusion_apply((int)s->store, ks, rec, n, ao->strength, col[j], nullptr, st);
+        if (e == hipSuccess) e = light_terms(s, algo, v, lights, n_lights, lj, c, state, col[j], st);
+        if (occlude && ao->apply == VR_AO_ALL && e == hipSuccess)
+            e = vr::launch_occlusion_apply((int)s->store, ks, rec, n, ao->strength, col[j], nullptr, st);
+        rays_prev = rays_j;
+    }
+    for (uint32_t j = depth; j >= 1u && e == hipSuccess; --j)
+        e = vr::launch_fold(list[j], cnt[j], col[j - 1], col[j], rf.reflectivity, st);
+    return e;
+}
+
+// The body of vr_shade_lights (ao null), vr_shade_lights_ao and vr_shade_lights_reflect (rf not
+// null; with a reflectivity or a depth of 0 it is vr_shade_lights_ao's call, kernel for kernel),
+// under the name `who` in every
 // message.  The occlusion pass (vr_occlusion.hip launch_occlusion_apply) runs over the records of
 // the primary walk -- the caller's, or an internal buffer when hits is NULL -- straight after the
 // primary kernel, when colors holds the ambient term alone (VR_AO_AMBIENT), or after the last
@@ -64,7 +145,7 @@ struct AoArgs {
 int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights,
                  const float ambient[3], const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
                  int inputs_on_device, uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream,
-                 const AoArgs* ao) {
+                 const AoArgs* ao, const ReflectArgs* rf = nullptr) {
     const std::string who(who_c);
     if (!s) return fail(VR_E_INVALID, who + ": scene is NULL");
     if (!translation) return fail(VR_E_INVALID, who + ": translation NULL");
@@ -78,6 +159,10 @@ int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_li
         return fail(VR_E_INVALID, who + ": unknown order");
     if (ao && ao->strength > 255u) return fail(VR_E_INVALID, who + ": ao_strength above 255");
     if (ao && ao->apply != VR_AO_AMBIENT && ao->apply != VR_AO_ALL) return fail(VR_E_INVALID, who + ": unknown ao_apply");
+    if (rf && rf->reflectivity > 255u) return fail(VR_E_INVALID, who + ": reflectivity above 255");
+    if (rf && rf->bounces > VR_MAX_BOUNCES) return fail(VR_E_INVALID, who + ": too many bounces (VR_MAX_BOUNCES)");
+    if (rf && (rf->value & ~rf->mask) != 0u)
+        return fail(VR_E_INVALID, who + ": mirror_value has bits outside mirror_mask (it could never match)");
     if (n == 0) return VR_OK;
     if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
         return fail(VR_E_INVALID, who + ": device rays must be 16-byte aligned");
@@ -125,14 +210,13 @@ int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_li
                                       rec, st);
     if (occlude && ao->apply == VR_AO_AMBIENT && e == hipSuccess)     // (colors holds the ambient term alone)
         e = vr::launch_occlusion_apply((int)s->store, vr::kscene(s), rec, (uint32_t)n, ao->strength, dc, da, st);
-    for (size_t k = 0; k < n_lights && e == hipSuccess; ++k) {
-        // light k as vr_shade takes it: the render's lighting block in the same view
-        vr::KView lv = v;
-        vr::view_lighting(lv, &lights[k]);
-        e = vr::launch_light_term((int)s->store, (int)algo, vr::kscene(s), lv, idx, (uint32_t)n, state, dc, st);
-    }
+    if (e == hipSuccess) e = light_terms(s, algo, v, lights, n_lights, idx, (uint32_t)n, state, dc, st);
     if (occlude && ao->apply == VR_AO_ALL && e == hipSuccess)
         e = vr::launch_occlusion_apply((int)s->store, vr::kscene(s), rec, (uint32_t)n, ao->strength, dc, da, st);
+    if (rf && rf->reflectivity != 0u && rf->bounces != 0u && e == hipSuccess) {
+        e = reflect_descend(sg, s, algo, v, lights, n_lights, ambient, ao, *rf, dr, (uint32_t)n, state, dc, st);
+        if (e == hipErrorOutOfMemory) return fail(VR_E_NOMEM, who + ": reflection buffers: " + std::string(hipGetErrorString(e)));
+    }
     if (e == hipSuccess && da && ao->out != da) {
         sg.fetch(ao->out, da, n * sizeof(uint32_t));
         e = sg.err;
@@ -298,6 +382,18 @@ int vr_shade_lights_ao(const vr_scene* s, vr_algo algo, const vr_lighting* light
                         inputs_on_device, colors, hits, outputs_on_device, order, stream, &ao);
 }
 
+// vr_shade_lights_ao with mirror reflections: the bounces' words folded into the first hit's (vr.h).
+int vr_shade_lights_reflect(const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights,
+                            const float ambient[3], const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
+                            int inputs_on_device, uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order,
+                            void* stream, uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out, uint32_t reflectivity,
+                            uint32_t bounces, uint32_t mirror_mask, uint32_t mirror_value) {
+    const AoArgs ao{ao_strength, ao_apply, ao_out};
+    const ReflectArgs rf{reflectivity, bounces, mirror_mask, mirror_value};
+    return shade_lights("vr_shade_lights_reflect", s, algo, lights, n_lights, ambient, translation, scale, rays, n,
+                        inputs_on_device, colors, hits, outputs_on_device, order, stream, &ao, &rf);
+}
+
 // How open the face of each hit is at the hit point (vr.h).
 int vr_occlusion(const vr_scene* s, const vr_hit* hits, size_t n, int inputs_on_device, uint32_t* ao, int outputs_on_device,
                  void* stream) {
@@ -320,6 +416,36 @@ int vr_occlusion(const vr_scene* s, const vr_hit* hits, size_t n, int inputs_on_
     if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_occlusion: ao buffer");
     const hipError_t e = vr::launch_occlusion((int)s->store, vr::kscene(s), dh, (uint32_t)n, da, st);
     return finish(sg, e, ao, da, n * sizeof(uint32_t), "vr_occlusion");
+}
+
+// The mirror bounce of each ray at its hit record (vr.h): needs no scene.
+int vr_bounce_rays(int device, const float translation[3], uint32_t scale, const vr_ray* rays, const vr_hit* hits, size_t n,
+                   int inputs_on_device, vr_ray* out, int outputs_on_device, void* stream) {
+    if (!translation) return fail(VR_E_INVALID, "vr_bounce_rays: translation NULL");
+    if (n && (!rays || !hits || !out)) return fail(VR_E_INVALID, "vr_bounce_rays: rays/hits/out NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_bounce_rays: too many records");
+    if (device < 0 || device > 63) return fail(VR_E_INVALID, "vr_bounce_rays: bad device");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && (((uintptr_t)rays | (uintptr_t)hits) & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_bounce_rays: device rays and hits must be 16-byte aligned");
+    if (outputs_on_device && ((uintptr_t)out & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_bounce_rays: device out must be 16-byte aligned");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(VR_E_INVALID, "vr_bounce_rays: no such device");
+    DeviceGuard dg(device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_bounce_rays")) return rc;
+    Staging sg(st);
+    const void *dr = rays, *dh = hits;
+    if (!inputs_on_device) {
+        dr = sg.upload(rays, n * sizeof(vr_ray));
+        dh = sg.upload(hits, n * sizeof(vr_hit));
+    }
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_bounce_rays: record upload");
+    void* dout = outputs_on_device ? out : sg.make(n * sizeof(vr_ray));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_bounce_rays: ray buffer");
+    const hipError_t e = vr::launch_bounce_rays(dr, dh, (uint32_t)n, translation, (float)scale, dout, st);
+    return finish(sg, e, out, dout, n * sizeof(vr_ray), "vr_bounce_rays");
 }
 
 // The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.

@@ -218,10 +218,11 @@ class DeviceScene:
                      hits=hits, stream=stream)
 
     def shade_lights(self, algorithm, info, lights, rays, ambient=None, order=None, hits: bool = False, stream=None,
-                     ao=None, ao_apply=None, return_ao: bool = False):
-        """vr_shade_lights (or, with ao=, vr_shade_lights_ao) with this scene: see shade_lights()."""
+                     ao=None, ao_apply=None, return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
+        """vr_shade_lights (or, with ao=, vr_shade_lights_ao; with reflect=, vr_shade_lights_reflect) with
+        this scene: see shade_lights()."""
         return shade_lights(self, algorithm, info, lights, rays, ambient=ambient, order=order, hits=hits, stream=stream,
-                            ao=ao, ao_apply=ao_apply, return_ao=return_ao)
+                            ao=ao, ao_apply=ao_apply, return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror)
 
     def occlusion(self, hits, stream=None):
         """vr_occlusion with this scene: see occlusion()."""
@@ -690,7 +691,7 @@ def occlusion(scene: DeviceScene, hits, stream=None):
 
 def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, lights, rays, ambient=None,
                  order: TraceOrder | None = None, hits: bool = False, stream=None, ao=None, ao_apply=None,
-                 return_ao: bool = False):
+                 return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
     """vr_shade_lights: shade() under several lights and an ambient term, from one primary walk per
     ray.  `lights` is a sequence of VrLighting blocks (at most VR_MAX_LIGHTS, possibly empty), each
     taken exactly as shade() takes its one; `ambient` is three floats or None.  colours[i] is, per
@@ -702,9 +703,18 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     ao (a strength 0..255, or None): vr_shade_lights_ao -- the ambient term (ao_apply
     AoApply.AMBIENT, the default) or the whole word (AoApply.ALL) scaled by the factor the strength
     makes of the hit's occlusion(); return_ao=True appends the occlusion values (as occlusion()
-    returns them) to the result.  With ao=None the call is vr_shade_lights."""
+    returns them) to the result.  With ao=None the call is vr_shade_lights.
+    reflect (a reflectivity 0..255, or None): vr_shade_lights_reflect -- mirror reflections, the
+    whole descent on the device: a ray whose hit voxel passes the mirror test bounces (bounce_rays())
+    up to `bounces` times (at most MAX_BOUNCES), each depth shaded as the first (lights, ambient, ao),
+    and the words are blended from the back, (first * (255 - reflect) + deeper * reflect + 127) // 255
+    per channel.  mirror = (mask, value): a voxel reflects when stored colour & mask == value; the
+    default (None) is every voxel.  hits and the occlusion values stay those of the first hit.  With
+    reflect=None the call is the one above, and bounces and mirror must be left alone."""
     if ao is None and (return_ao or ao_apply is not None):
         raise ValueError("ao_apply and return_ao need ao= (a strength 0..255)")
+    if reflect is None and (mirror is not None or int(bounces) != 1):
+        raise ValueError("bounces and mirror need reflect= (a reflectivity 0..255)")
     lights = list(lights)
     block = (_capi.VrLighting * max(len(lights), 1))(*lights)
     if ambient is not None and len(ambient) != 3:
@@ -718,6 +728,19 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     recs = _records(n, HIT_DTYPE, rays) if hits else None
     tail = (_ptr(rays), n, dev, _ptr(colors), _ptr(recs) if hits else None, dev,
             int(TraceOrder.AUTO if order is None else order), _stream_ptr(stream))
+    if reflect is not None:
+        strength, apply = int(0 if ao is None else ao), int(AoApply.AMBIENT if ao_apply is None else ao_apply)
+        refl = (int(reflect), int(bounces)) + ((0, 0) if mirror is None else (int(mirror[0]), int(mirror[1])))
+        if any(not 0 <= x < 1 << 32 for x in (strength, apply) + refl):
+            raise ValueError("reflect, bounces, mirror, ao and ao_apply must be unsigned 32-bit values")
+        values = None
+        if return_ao:
+            values = torch.empty(n, dtype=torch.int32, device=rays.device) if dev else np.zeros(n, dtype=np.uint32)
+        # (the library refuses what it refuses with its message, rays or none)
+        check(lib().vr_shade_lights_reflect(*args, *tail, strength, apply, _ptr(values) if return_ao else None, *refl),
+              "vr_shade_lights_reflect")
+        out = (colors,) + ((recs,) if hits else ()) + ((values,) if return_ao else ())
+        return out if len(out) > 1 else colors
     if ao is None:
         if len(lights) > _capi.VR_MAX_LIGHTS or n:     # (the library refuses too many lights, with its message)
             check(lib().vr_shade_lights(*args, *tail), "vr_shade_lights")
@@ -750,7 +773,7 @@ def _tile_order_pixels(width: int, height: int, device):
 
 def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, lights,
                   width: int, height: int, ambient=None, stream=None, samples: int = 1, ao=None, ao_apply=None,
-                  return_ao: bool = False):
+                  return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
     """A width x height frame under several lights and an ambient term: shade_lights() of the
     frame's camera_rays(), as a (height, width) int32 CUDA tensor of 0x00RRGGBB words on the
     scene's device.  The rays are taken in 8 x 8-tile order (row-major rays measured 18-26 %
@@ -762,13 +785,16 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
     ao, ao_apply: shade_lights()'s, for every ray of the frame (of the fine frame with samples > 1).
     return_ao=True returns (frame, values): the occlusion values of the frame's pixels as a
     (height, width) int32 CUDA tensor -- of the fine frame's, (samples * height, samples * width),
-    with samples > 1 (they are not filtered)."""
+    with samples > 1 (they are not filtered).
+    reflect, bounces, mirror: shade_lights()'s mirror reflections, for every ray of the frame (of the
+    fine frame with samples > 1)."""
     samples = int(samples)
     if samples != 1:
         if samples not in (2, 4, 8):
             raise ValueError("samples must be 1, 2, 4 or 8")
         fine = render_lights(scene, algorithm, camera, info, lights, samples * int(width), samples * int(height),
-                             ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply, return_ao=return_ao)
+                             ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply, return_ao=return_ao,
+                             reflect=reflect, bounces=bounces, mirror=mirror)
         if return_ao:
             return resolve(fine[0], width, height, samples, stream=stream), fine[1]
         return resolve(fine, width, height, samples, stream=stream)
@@ -778,7 +804,7 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
         px, py = _tile_order_pixels(int(width), int(height), device)
         rays = camera_rays(camera, width, height, px, py, device=device.index, stream=stream)
         words = shade_lights(scene, algorithm, info, lights, rays, ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply,
-                             return_ao=return_ao)
+                             return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror)
         frame = torch.empty((int(height), int(width)), dtype=torch.int32, device=device)
         frame[py.long(), px.long()] = words[0] if return_ao else words
         if return_ao:
@@ -877,6 +903,40 @@ def camera_rays(camera: Camera, width: int, height: int, px, py, device: int = 0
         check(lib().vr_camera_rays(*args, _ptr(px), _ptr(py), n, dev, _ptr(rays), dev, _stream_ptr(stream)),
               "vr_camera_rays")
     return rays
+
+
+MAX_BOUNCES = _capi.VR_MAX_BOUNCES
+
+
+def bounce_rays(rays, hits, info: VoxelSceneInfo, device: int = 0, stream=None):
+    """vr_bounce_rays: the mirror bounce of rays[i] at the hit record hits[i] -- origin the hit point
+    back in world units, info.translation + (region * 64 + point) / info.scale, direction the
+    incoming one with the sign of the hit normal's axis flipped (not normalised).  A record that is
+    no VOXEL hit with a unit axis normal gives an all-NaN ray, which is not harmless to trace: mask
+    what you trace by the records' status.  No mirror test is applied.  numpy rays (a RAY_DTYPE
+    array or (n, 6)) with a HIT_DTYPE array give a RAY_DTYPE array; CUDA tensors -- float32 (n, 8) or
+    (n, 6) rays and (n, 16) int32 records on one device -- give an (n, 8) float32 CUDA tensor there
+    (`device` is then not used).  Needs no scene."""
+    dev = int(hasattr(rays, "is_cuda") and rays.is_cuda)
+    if dev:
+        if not (hasattr(hits, "is_cuda") and hits.is_cuda) or hits.device != rays.device:
+            raise TypeError("rays and hits must both be CUDA tensors on one device, or both numpy arrays")
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 16:
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        rays, hits = _rays_cuda(rays), hits.contiguous()
+        device = rays.device.index
+    else:
+        if not (isinstance(hits, np.ndarray) and hits.dtype == HIT_DTYPE):
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        rays, hits = _rays_numpy(rays), np.ascontiguousarray(hits).reshape(-1)
+    n = rays.shape[0]
+    if hits.shape[0] != n:
+        raise ValueError("rays and hits lengths differ")
+    out = _records(n, RAY_DTYPE, rays)
+    if n:
+        check(lib().vr_bounce_rays(int(device), f3(info.translation), int(info.scale), _ptr(rays), _ptr(hits), n, dev,
+                                   _ptr(out), dev, _stream_ptr(stream)), "vr_bounce_rays")
+    return out
 
 
 def band_buffer_words(width: int, height: int, band_rows: int, nranks: int) -> int:
