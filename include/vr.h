@@ -587,6 +587,95 @@ int vr_shade_lights_reflect(const vr_scene* s, vr_algo algo,
                             uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out /* may be NULL */,
                             uint32_t reflectivity, uint32_t bounces, uint32_t mirror_mask, uint32_t mirror_value);
 
+/* Sky and distance fog: what a ray that hits nothing sees, and how a hit fades with its distance.
+ * A vr_atmosphere is plain data: nothing in it is rejected but unknown flag bits, and nothing is
+ * normalised. */
+#define VR_ATMOS_SKY 1u   /* a MISS shows the sky in the direction of its ray */
+#define VR_ATMOS_FOG 2u   /* a VOXEL hit is blended towards fog_color by its distance */
+typedef struct {
+    float zenith[3], horizon[3], nadir[3];  /* sky colours, 1.0 = 255, plain data */
+    float up[3];                            /* plain data, NOT normalised by the library */
+    float fog_color[3];
+    float fog_start, fog_end;               /* world units, plain data */
+    uint32_t flags;                         /* VR_ATMOS_SKY | VR_ATMOS_FOG */
+    uint32_t reserved;                      /* 0 */
+} vr_atmosphere;
+/* A daylight sky: zenith (0.25, 0.45, 0.85), horizon (0.75, 0.85, 0.95), nadir (0.30, 0.28, 0.25),
+ * up (0, 1, 0), fog_color the horizon's, fog_start 0, fog_end 16, flags VR_ATMOS_SKY (fog off),
+ * reserved 0.  VR_E_INVALID for NULL. */
+int vr_atmosphere_default(vr_atmosphere* atm);
+
+/* out[i] = atmos(colors_in[i], rays[i], hits[i]): the colour word of a ray under an atmosphere.  It
+ * takes the records of vr_pick, vr_trace, vr_shade and vr_shade_lights, and records the caller made
+ * up: no record and no ray is rejected and any 64 bytes are safe.
+ *
+ * All floating-point arithmetic is fp32, each operation rounded on its own in the order written
+ * (the parentheses are the order), no contraction, divisions and square roots correctly rounded.
+ *   colour bytes  byte(x) = min(255, f2u(x * 255.0f)), f2u as in vr_shade_lights' ambient term: NaN
+ *                 and values <= 0 give 0, everything else truncates.  Z, H, N and F are the words
+ *                 byte(c[0]) << 16 | byte(c[1]) << 8 | byte(c[2]) of zenith, horizon, nadir and
+ *                 fog_color, made once per call.
+ *   q256(f)       g = f * 256.0f; 0 if !(g > 0) (NaN too), 256 if g >= 256, else (int)g, truncated:
+ *                 vr_occlusion's position rule.
+ *   lerp256(a, b, q)  each of the bytes R, G and B is (A * (256 - q) + B * q + 128) >> 8; bits 24-31
+ *                 are dropped.  q = 0 gives a and q = 256 gives b (below 2^24).
+ *   sky(d)        for a ray direction d of any length: len = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z),
+ *                 h = ((d.x*up.x + d.y*up.y) + d.z*up.z) / len,
+ *                 sky = lerp256(H, h < 0 ? N : Z, q256(fabsf(h))).  A zero, infinite or NaN direction
+ *                 gives whatever these operations give; a NaN h gives H.
+ *   fog(w, ray, h)  p[c] = translation[c] + (((float)h.region[c] * 64.0f + h.point[c]) / (float)scale),
+ *                 vr_bounce_rays' origin: the hit point back in world space; e[c] = p[c] - ray.origin[c];
+ *                 D = sqrtf((e.x*e.x + e.y*e.y) + e.z*e.z);
+ *                 f = (D - fog_start) / (fog_end - fog_start); fog = lerp256(w, F, q256(f)).
+ *                 fog_end <= fog_start is taken as data: a step or an inverted ramp, as the operations
+ *                 say.  The fog needs no unit normal: every VOXEL record has it.
+ *   atmos(w, ray, h)  h.status == VR_HIT_MISS and flags has VR_ATMOS_SKY: sky(ray.direction);
+ *                 h.status == VR_HIT_VOXEL and flags has VR_ATMOS_FOG: fog(w, ray, h);
+ *                 every other case (NEVER, OUTSIDE, an unknown status, a flag not set): w, bit for bit.
+ * The fog is linear on purpose: an exponential needs an exp that two implementations would not
+ * share to the bit.
+ *
+ * Runs on `device` (no scene is needed) as one small kernel on `stream`, one lane per record, with
+ * 16-byte loads of rays and records.  rays, hits and colors_in are all host arrays, or all on the
+ * device (rays and hits 16-byte, colors_in 4-byte aligned) when inputs_on_device != 0; colors_out is
+ * on the device (4-byte aligned) when outputs_on_device != 0, and may then be colors_in itself; host
+ * arrays are staged as vr_bounce_rays stages them.  Returns when colors_out[0..n) are written.
+ * n == 0 returns VR_OK.  Not a render launch.
+ *
+ * VR_E_INVALID (nothing is written): atm or translation NULL; atm->flags with a bit other than
+ * VR_ATMOS_SKY | VR_ATMOS_FOG; rays, hits, colors_in or colors_out NULL with n > 0; n >= 2^31;
+ * device outside 0..63 or not present; a misaligned device array; a stream that is capturing a HIP
+ * graph. */
+int vr_atmosphere_apply(int device, const vr_atmosphere* atm, const float translation[3], uint32_t scale,
+                        const vr_ray* rays, const vr_hit* hits, const uint32_t* colors_in, size_t n,
+                        int inputs_on_device, uint32_t* colors_out, int outputs_on_device, void* stream);
+
+/* vr_shade_lights_reflect under an atmosphere, on the device: with atm == NULL or atm->flags == 0
+ * the call is vr_shade_lights_reflect kernel for kernel -- no extra launch, allocation or readback.
+ * Otherwise A^j_i = atmos(W^j_i, ray^j_i, H^j_i) (vr_atmosphere_apply above) replaces W^j_i everywhere
+ * in vr_shade_lights_reflect's fold:
+ *   C^B_i = A^B_i,   C^j_i = refl^j_i ? mix(A^j_i, C^(j+1)_i, k) : A^j_i,   colors[i] = C^0_i.
+ * The fog is per leg: a bounce ray's origin is the previous hit point, so D is the length of that
+ * leg alone.  A miss at any depth shows the sky in the direction of that depth's ray: a mirror
+ * shows the sky.  The mirror test, hits and ao_out are untouched: they read stored colours and
+ * records, never the tinted word.  A walk that never ends keeps its word 0.
+ *
+ * One more small kernel per depth reached runs on `stream`, after that depth's last colour pass; it
+ * allocates nothing.  Every other argument is vr_shade_lights_reflect's.
+ *
+ * VR_E_INVALID (nothing is written; every check comes before any device work):
+ * vr_shade_lights_reflect's cases; atm->flags with a bit other than VR_ATMOS_SKY | VR_ATMOS_FOG. */
+int vr_shade_lights_atmosphere(const vr_scene* s, vr_algo algo,
+                               const vr_lighting* lights, size_t n_lights,
+                               const float ambient[3] /* may be NULL */,
+                               const float translation[3], uint32_t scale,
+                               const vr_ray* rays, size_t n, int inputs_on_device,
+                               uint32_t* colors, vr_hit* hits /* may be NULL */, int outputs_on_device,
+                               uint32_t order, void* stream,
+                               uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out /* may be NULL */,
+                               uint32_t reflectivity, uint32_t bounces, uint32_t mirror_mask, uint32_t mirror_value,
+                               const vr_atmosphere* atm /* may be NULL */);
+
 /* The ray a render or pick walks for pixel (px[i], py[i]) of a width x height frame (y = 0 the
  * top row): origin is the image-plane point lower_left + u * horizontal + v * vertical, with
  * the render's bits; direction is origin - cam->origin, NOT normalised -- vr_trace applies the

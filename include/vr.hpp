@@ -316,6 +316,52 @@ inline std::vector<uint32_t> shadeLightsReflect(RayMarchAlgorithm algo, const Vo
     return colors;
 }
 
+// vr_atmosphere_default: a daylight sky with up = (0, 1, 0), fog off.
+inline vr_atmosphere atmosphereDefault() {
+    vr_atmosphere atm;
+    check(vr_atmosphere_default(&atm), "atmosphereDefault");
+    return atm;
+}
+
+// vr_atmosphere_apply: colors[i] under the atmosphere -- the sky in the direction of rays[i] where
+// hits[i] is a MISS (VR_ATMOS_SKY), colors[i] blended towards the fog's colour by the distance from
+// rays[i]'s origin to the hit point where it is a VOXEL record (VR_ATMOS_FOG), colors[i] otherwise.
+inline std::vector<uint32_t> atmosphereApply(const VoxelSceneInfo& info, const vr_atmosphere& atm,
+                                             const std::vector<vr_ray>& rays, const std::vector<vr_hit>& hits,
+                                             const std::vector<uint32_t>& colors, int device = 0, void* stream = nullptr) {
+    if (rays.size() != hits.size() || rays.size() != colors.size())
+        throw Error(VR_E_INVALID, "atmosphereApply: rays, hits and colors lengths differ");
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> out(rays.size());
+    check(vr_atmosphere_apply(device, &atm, t, info.scale, rays.data(), hits.data(), colors.data(), rays.size(), 0, out.data(), 0,
+                              stream),
+          "atmosphereApply");
+    return out;
+}
+
+// vr_shade_lights_atmosphere: shadeLightsReflect() (reflectivity 0: shadeLightsAo()) under a sky and
+// a distance fog -- at every depth a miss shows the sky in the direction of that depth's ray and a
+// hit fades with the length of its leg, before the depths are blended.  hits and aoOut are untouched.
+inline std::vector<uint32_t> shadeLightsAtmosphere(RayMarchAlgorithm algo, const VoxelSceneInfo& info,
+                                                   const std::vector<vr_lighting>& lights, const float* ambient,
+                                                   const DeviceScene& scene, const std::vector<vr_ray>& rays,
+                                                   const vr_atmosphere& atm, uint32_t reflectivity = 0, uint32_t bounces = 1,
+                                                   uint32_t mirrorMask = 0, uint32_t mirrorValue = 0, uint32_t aoStrength = 0,
+                                                   vr_ao_apply aoApply = VR_AO_AMBIENT, std::vector<uint32_t>* aoOut = nullptr,
+                                                   std::vector<vr_hit>* hits = nullptr,
+                                                   vr_trace_order order = VR_TRACE_ORDER_AUTO, void* stream = nullptr) {
+    float t[3] = {info.translationVector.x, info.translationVector.y, info.translationVector.z};
+    std::vector<uint32_t> colors(rays.size());
+    if (hits) hits->assign(rays.size(), vr_hit{});
+    if (aoOut) aoOut->assign(rays.size(), VR_AO_OPEN);
+    check(vr_shade_lights_atmosphere(scene.get(), (vr_algo)algo, lights.data(), lights.size(), ambient, t, info.scale,
+                                     rays.data(), rays.size(), 0, colors.data(), hits ? hits->data() : nullptr, 0,
+                                     (uint32_t)order, stream, aoStrength, (uint32_t)aoApply, aoOut ? aoOut->data() : nullptr,
+                                     reflectivity, bounces, mirrorMask, mirrorValue, &atm),
+          "shadeLightsAtmosphere");
+    return colors;
+}
+
 // vr_camera_rays: the rays a render or pick walks for pixels (px[i], py[i]) of a width x height
 // frame; trace(camera_rays(px, py)) equals pick(px, py) for pixels inside the frame.
 inline std::vector<vr_ray> camera_rays(uint32_t width, uint32_t height, const Camera& camera, const std::vector<uint32_t>& px,

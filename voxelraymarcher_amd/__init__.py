@@ -15,12 +15,12 @@ from .renderer import (CONFIGS, HIT_DTYPE, VOXEL_ABSENT, VOXEL_REMOVE, Build, Hi
                        create_scene, deal_stride_default, debug_capture_lane_order, debug_force_in_flight, debug_lane_order, debug_lane_order_from, debug_last_launch,
                        debug_order_uses, debug_skip_next_crawl, debug_work_order, debug_work_order_from,
                        forget_orders, pack_rgb8, pick, parse_algorithm, parse_storage, RAY_DTYPE, TraceOrder, camera_rays, shade, trace,
-                       render_lights, shade_lights, occlusion, AoApply, AO_OPEN, bounce_rays, MAX_BOUNCES, render_aa, resolve, aa_fine_words, read_voxel_file, render_bands, render_count, render_ex, render_tiles, run_raymarching_kernel,
+                       render_lights, shade_lights, occlusion, AoApply, AO_OPEN, bounce_rays, MAX_BOUNCES, Atmosphere, atmosphere_apply, atmosphere_default, render_aa, resolve, aa_fine_words, read_voxel_file, render_bands, render_count, render_ex, render_tiles, run_raymarching_kernel,
                        setup_constant_values, synth_scene, tile_buffer_words, write_binary_scene, write_voxel_file)
 
 __all__ = ["LIB_PATH", "VrError", "lib", "FrameWriter", "ImageWriter", "encode_png", "write_png", "CONFIGS", "HIT_DTYPE", "HitStatus",
            "VOXEL_ABSENT", "VOXEL_REMOVE", "Build", "pick", "RAY_DTYPE", "TraceOrder", "camera_rays", "shade", "trace",
-           "render_lights", "shade_lights", "occlusion", "AoApply", "AO_OPEN", "bounce_rays", "MAX_BOUNCES", "render_aa", "resolve", "aa_fine_words", "Camera", "DeviceScene", "Kernel", "Occupancy", "PreparedRender", "RayMarchAlgorithm", "RenderConfig", "Schedule",
+           "render_lights", "shade_lights", "occlusion", "AoApply", "AO_OPEN", "bounce_rays", "MAX_BOUNCES", "Atmosphere", "atmosphere_apply", "atmosphere_default", "render_aa", "resolve", "aa_fine_words", "Camera", "DeviceScene", "Kernel", "Occupancy", "PreparedRender", "RayMarchAlgorithm", "RenderConfig", "Schedule",
            "StorageType", "VoxelSceneCPU", "VoxelSceneInfo", "assemble_tiles_device", "band_buffer_words",
            "create_scene", "deal_stride_default", "debug_capture_lane_order", "debug_force_in_flight", "debug_lane_order", "debug_lane_order_from", "debug_last_launch",
            "debug_order_uses", "debug_work_order", "debug_work_order_from",

@@ -86,6 +86,15 @@ VR_AO_AMBIENT, VR_AO_ALL = 0, 1
 
 VR_MAX_BOUNCES = 4
 
+VR_ATMOS_SKY, VR_ATMOS_FOG = 1, 2
+
+
+class VrAtmosphere(ctypes.Structure):
+    """vr_atmosphere: the sky's colours, up, and the distance fog (76 bytes, plain data)."""
+    _fields_ = [("zenith", c_float * 3), ("horizon", c_float * 3), ("nadir", c_float * 3), ("up", c_float * 3),
+                ("fog_color", c_float * 3), ("fog_start", c_float), ("fog_end", c_float), ("flags", c_uint32),
+                ("reserved", c_uint32)]
+
 
 class VrError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str):
@@ -156,6 +165,13 @@ SIGNATURES = {
     "vr_shade_lights_reflect": (c_int, [c_void_p, c_int, POINTER(VrLighting), c_size_t, POINTER(c_float), POINTER(c_float),
                                         c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_uint32, c_void_p,
                                         c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32]),
+    "vr_atmosphere_default": (c_int, [POINTER(VrAtmosphere)]),
+    "vr_atmosphere_apply": (c_int, [c_int, POINTER(VrAtmosphere), POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "vr_shade_lights_atmosphere": (c_int, [c_void_p, c_int, POINTER(VrLighting), c_size_t, POINTER(c_float), POINTER(c_float),
+                                           c_uint32, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_uint32, c_void_p,
+                                           c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
+                                           POINTER(VrAtmosphere)]),
     "vr_camera_rays": (c_int, [c_int, POINTER(VrCamera), c_uint32, c_uint32, c_void_p, c_void_p, c_size_t, c_int,
                                c_void_p, c_int, c_void_p]),
     "vr_pack_rgb8": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
@@ -208,6 +224,7 @@ __all__ = ["lib", "check", "VrCamera", "VrLighting", "VrRenderOpts", "VR_RENDER_
            "VR_SCHEDULE_HEAVIEST_FIRST", "VR_OCCUPANCY_AUTO", "VR_OCCUPANCY_LONE", "VR_OCCUPANCY_IN_FLIGHT",
            "VrSceneInfo", "VrSynthParams", "VrHit", "VR_HIT_MISS",
            "VR_HIT_VOXEL", "VR_HIT_NEVER", "VR_HIT_OUTSIDE", "VrRay", "VR_TRACE_ORDER_AUTO",
-           "VR_TRACE_ORDER_GIVEN", "VR_TRACE_ORDER_COHERENT", "VR_MAX_LIGHTS", "VR_AO_OPEN", "VR_AO_AMBIENT", "VR_AO_ALL", "VR_MAX_BOUNCES", "VrError", "SIGNATURES",
+           "VR_TRACE_ORDER_GIVEN", "VR_TRACE_ORDER_COHERENT", "VR_MAX_LIGHTS", "VR_AO_OPEN", "VR_AO_AMBIENT", "VR_AO_ALL", "VR_MAX_BOUNCES", "VR_ATMOS_SKY", "VR_ATMOS_FOG",
+           "VrAtmosphere", "VrError", "SIGNATURES",
            "VR_STORE_VCS", "VR_STORE_HASHTABLE", "VR_ALGO_LONGESTAXIS", "VR_ALGO_ORIGINAL", "f3", "LIB_PATH",
            "c_uint8"]

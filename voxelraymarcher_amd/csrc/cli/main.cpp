@@ -46,6 +46,16 @@
 //                                 --reflect selects the lights frame as --ambient does and works with
 //                                 --add-light, --ambient, --ao and --aa; the "lights" line then ends in
 //                                 " reflect <K> bounces <B> mirror <every|rrggbb>"; not with --gpus)
+//                   [--sky ZZZZZZ,HHHHHH,NNNNNN] [--fog RRGGBB,START,END]  (sky and distance fog,
+//                                 vr_shade_lights_atmosphere: --sky gives the colours (hex) a ray that
+//                                 hits nothing shows straight up, level and straight down, up being
+//                                 (0, 1, 0); --fog blends every hit towards RRGGBB between START and END
+//                                 world units from its ray's origin; a colour byte b is handed over as
+//                                 the float (b + 0.5) / 255, which the library truncates back to b;
+//                                 either selects the lights frame as --ambient does and works with
+//                                 --add-light, --ambient, --ao, --reflect and --aa; the "lights" line
+//                                 then ends in " sky <zzzzzz> <hhhhhh> <nnnnnn>" and / or
+//                                 " fog <rrggbb> <start> <end>"; not with --gpus)
 //                   [--aa S]     (S = 1, 2, 4 or 8 samples per axis: output.png is the resolved frame --
 //                                 the (S * width) x (S * height) render box-filtered with round half
 //                                 up, vr_render_aa; with --add-light / --ambient the lights frame is
@@ -58,6 +68,7 @@
 // around launch + sync, :114,160-162).
 #include <hip/hip_runtime.h>
 
+#include <cctype>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -186,6 +197,25 @@ int main(int argc, char* argv[]) {
     uint32_t ao_strength = 0;
     bool has_reflect = false, has_bounces = false, has_mirror = false;     // --reflect K, --bounces B, --mirror RRGGBB
     uint32_t reflect_k = 0, bounces = 1, mirror_rgb = 0;
+    bool has_sky = false, has_fog = false;   // --sky ZZZZZZ,HHHHHH,NNNNNN, --fog RRGGBB,START,END
+    uint32_t sky_rgb[3] = {0, 0, 0}, fog_rgb = 0;
+    float fog_start = 0.0f, fog_end = 0.0f;
+    // RRGGBB: one to six hexadecimal digits and nothing else
+    auto parse_rgb = [](const std::string& v, uint32_t& out) {
+        if (v.empty() || v.size() > 6) return false;
+        for (const char c : v)
+            if (!std::isxdigit((unsigned char)c)) return false;
+        out = (uint32_t)std::strtoul(v.c_str(), nullptr, 16);
+        return true;
+    };
+    auto split_commas = [](const char* v) {
+        std::vector<std::string> parts(1);
+        for (const char* c = v; *c; ++c) {
+            if (*c == ',') parts.emplace_back();
+            else parts.back().push_back(*c);
+        }
+        return parts;
+    };
     float light_pos[3] = {10.0f, 10.0f, -10.0f}, light_dir[3] = {1.0f, 1.0f, 1.0f}, light_color[3] = {1.0f, 1.0f, 1.0f};
     auto vec3 = [](const char* name, const char* v, float out[3]) {
         if (!parse_vec3(v, out)) { std::cerr << name << " needs X,Y,Z" << std::endl; std::exit(2); }
@@ -315,13 +345,38 @@ int main(int argc, char* argv[]) {
             mirror_rgb = (uint32_t)c;
             has_mirror = true;
         }
+        else if (a == "--sky") {
+            const std::vector<std::string> parts = split_commas(next("--sky"));
+            if (parts.size() != 3 || !parse_rgb(parts[0], sky_rgb[0]) || !parse_rgb(parts[1], sky_rgb[1]) ||
+                !parse_rgb(parts[2], sky_rgb[2])) {
+                std::cerr << "--sky needs ZZZZZZ,HHHHHH,NNNNNN (zenith, horizon and nadir colours, hex)" << std::endl;
+                std::exit(2);
+            }
+            has_sky = true;
+        }
+        else if (a == "--fog") {
+            const std::vector<std::string> parts = split_commas(next("--fog"));
+            char *e1 = nullptr, *e2 = nullptr;
+            bool ok = parts.size() == 3 && parse_rgb(parts[0], fog_rgb) && !parts[1].empty() && !parts[2].empty();
+            if (ok) {
+                fog_start = std::strtof(parts[1].c_str(), &e1);
+                fog_end = std::strtof(parts[2].c_str(), &e2);
+                ok = *e1 == '\0' && *e2 == '\0';
+            }
+            if (!ok) {
+                std::cerr << "--fog needs RRGGBB,START,END (the fog's colour, hex, and its bounds in world units)" << std::endl;
+                std::exit(2);
+            }
+            has_fog = true;
+        }
         else if (a == "-h" || a == "--help") {
             std::cout << "usage: VoxelRaymarcher [scale] {hashtable|vcs} {original|longestaxis} [--scene F] "
                          "[--width W] [--height H] [--out F] [--device N] [--synth N] [--repeat K] [--write-vxb F] "
                          "[--no-shadows] [--point-light X,Y,Z] [--light-dir X,Y,Z] [--light-color R,G,B] [--gpus N] "
                          "[--pick X,Y]... [--trace OX,OY,OZ,DX,DY,DZ]... [--shade OX,OY,OZ,DX,DY,DZ]... "
                          "[--lookup X,Y,Z]... [--paint X,Y,Z,RRGGBB]... [--add-light DX,DY,DZ,R,G,B]... "
-                         "[--ambient R,G,B] [--ao STRENGTH] [--ao-all] [--reflect K] [--bounces B] [--mirror RRGGBB] [--aa S]" << std::endl;
+                         "[--ambient R,G,B] [--ao STRENGTH] [--ao-all] [--reflect K] [--bounces B] [--mirror RRGGBB] "
+                         "[--sky ZZZZZZ,HHHHHH,NNNNNN] [--fog RRGGBB,START,END] [--aa S]" << std::endl;
             return 0;
         } else pos.push_back(argv[i]);
     }
@@ -363,9 +418,11 @@ int main(int argc, char* argv[]) {
         std::cerr << "ERROR: --bounces and --mirror need --reflect K" << std::endl;
         return 2;
     }
-    const bool lights_frame = !added_lights.empty() || has_ambient || has_ao || has_reflect;
+    const bool has_atmos = has_sky || has_fog;
+    const bool lights_frame = !added_lights.empty() || has_ambient || has_ao || has_reflect || has_atmos;
     if (lights_frame && multi) {             // (the frame is one device's vr_shade_lights call)
-        std::cerr << "ERROR: --add-light, --ambient, --ao and --reflect shade a single-GPU frame: not with --gpus" << std::endl;
+        std::cerr << "ERROR: --add-light, --ambient, --ao, --reflect, --sky and --fog shade a single-GPU frame: not with --gpus"
+                  << std::endl;
         return 2;
     }
     if (aa && multi) {                       // (a resolved frame dealt over several GPUs: a later change)
@@ -613,7 +670,30 @@ int main(int argc, char* argv[]) {
             const float t[3] = {sinfo.translationVector.x, sinfo.translationVector.y, sinfo.translationVector.z};
             std::vector<uint32_t> words(n), frame(n);
             int rc = vr_camera_rays(device, &camera.raw(), lw, lh, px.data(), py.data(), n, 0, rays, 1, nullptr);
-            if (rc == VR_OK && has_reflect)
+            if (rc == VR_OK && has_atmos) {
+                // (a byte b as (b + 0.5) / 255: the library's truncation gives b back)
+                vr_atmosphere atm = vrx::atmosphereDefault();
+                const auto put = [](float out[3], uint32_t rgb) {
+                    for (int c = 0; c < 3; ++c) out[c] = ((float)((rgb >> (16 - 8 * c)) & 0xFFu) + 0.5f) / 255.0f;
+                };
+                if (has_sky) {
+                    put(atm.zenith, sky_rgb[0]);
+                    put(atm.horizon, sky_rgb[1]);
+                    put(atm.nadir, sky_rgb[2]);
+                }
+                if (has_fog) {
+                    put(atm.fog_color, fog_rgb);
+                    atm.fog_start = fog_start;
+                    atm.fog_end = fog_end;
+                }
+                atm.flags = (has_sky ? VR_ATMOS_SKY : 0u) | (has_fog ? VR_ATMOS_FOG : 0u);
+                rc = vr_shade_lights_atmosphere(scene.get(), (vr_algo)algo, lights.data(), lights.size(),
+                                                has_ambient ? ambient : nullptr, t, sinfo.scale, rays, n, 1, words.data(), nullptr,
+                                                0, VR_TRACE_ORDER_AUTO, nullptr, has_ao ? ao_strength : 0u,
+                                                ao_all ? VR_AO_ALL : VR_AO_AMBIENT, nullptr, has_reflect ? reflect_k : 0u,
+                                                has_reflect ? bounces : 0u, has_mirror ? 0xFFFFFFu : 0u,
+                                                has_mirror ? mirror_rgb : 0u, &atm);
+            } else if (rc == VR_OK && has_reflect)
                 rc = vr_shade_lights_reflect(scene.get(), (vr_algo)algo, lights.data(), lights.size(),
                                              has_ambient ? ambient : nullptr, t, sinfo.scale, rays, n, 1, words.data(), nullptr,
                                              0, VR_TRACE_ORDER_AUTO, nullptr, has_ao ? ao_strength : 0u,
@@ -636,6 +716,8 @@ int main(int argc, char* argv[]) {
             if (has_ao) std::printf(" ao %u %s", ao_strength, ao_all ? "all" : "ambient");
             if (has_reflect && has_mirror) std::printf(" reflect %u bounces %u mirror %06x", reflect_k, bounces, mirror_rgb);
             else if (has_reflect) std::printf(" reflect %u bounces %u mirror every", reflect_k, bounces);
+            if (has_sky) std::printf(" sky %06x %06x %06x", sky_rgb[0], sky_rgb[1], sky_rgb[2]);
+            if (has_fog) std::printf(" fog %06x %.9g %.9g", fog_rgb, fog_start, fog_end);
             std::printf("\n");
             std::fflush(stdout);
         }

@@ -263,6 +263,17 @@ hipError_t launch_bounce_compact(const void* state, const void* rays_in, const u
 // shallow[r] = mix_rgb(shallow[r], deep[r], k) for the n rays r of list (k in 0..255).
 hipError_t launch_fold(const uint32_t* list, uint32_t n, uint32_t* shallow, const uint32_t* deep, uint32_t k,
                        hipStream_t stream);
+// (vr_atmos.hip: sky and distance fog; AtmosParams: vr_atmos_math.h)
+struct AtmosParams;
+// vr_shade_lights_atmosphere's pass for one depth, after that depth's last colour pass on the same
+// stream: colors[r] = atmos(colors[r], rays[r], the hit state of r) for the n rays r = list[i]
+// (list null: r = i).  state and rays are 16-byte aligned device memory indexed by ray number.
+hipError_t launch_atmos_state(const void* state, const void* rays, const uint32_t* list, uint32_t n, const AtmosParams& p,
+                              const float translation[3], float scale_f, uint32_t* colors, hipStream_t stream);
+// vr_atmosphere_apply's kernel: out[i] = atmos(in[i], rays[i], hits[i]) for n records, one lane per
+// record; rays and hits are 16-byte aligned device memory; out may be in.
+hipError_t launch_atmos_records(const void* rays, const void* hits, const uint32_t* in, uint32_t n, const AtmosParams& p,
+                                const float translation[3], float scale_f, uint32_t* out, hipStream_t stream);
 // (vr_util.hip, to launch_assemble_tiles)
 // vcs_cbits of a VCS scene from its mask records (one thread per 32 cluster slots).
 hipError_t launch_cluster_bits(const uint2* vcs_mask, uint32_t n_regions, uint32_t* cbits, hipStream_t stream);

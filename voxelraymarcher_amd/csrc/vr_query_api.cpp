@@ -1,13 +1,15 @@
 // vr_query_api.cpp -- the query entry points of include/vr.h: vr_pick, vr_trace, vr_shade,
-// vr_shade_lights, vr_shade_lights_ao, vr_shade_lights_reflect, vr_occlusion, vr_bounce_rays and
-// vr_camera_rays (their kernels: vr_query.hip, vr_trace.hip, vr_shade.hip, vr_lights.hip,
-// vr_occlusion.hip, vr_reflect.hip).  None is a render launch: no slot
+// vr_shade_lights, vr_shade_lights_ao, vr_shade_lights_reflect, vr_shade_lights_atmosphere,
+// vr_occlusion, vr_bounce_rays, vr_atmosphere_apply and vr_camera_rays (their kernels: vr_query.hip,
+// vr_trace.hip, vr_shade.hip, vr_lights.hip, vr_occlusion.hip, vr_reflect.hip, vr_atmos.hip).  None
+// is a render launch: no slot
 // lease, no view key, nothing the render path keeps per device (vr_launch.cpp) is touched.  Each
 // takes its arrays on the host or on the device (vr_staging.h), and in each every argument
 // check comes before any device work.
 #include <cstddef>
 #include <cstring>
 
+#include "vr_atmos_math.h"
 #include "vr_host.h"
 #include "vr_staging.h"
 
@@ -61,6 +63,13 @@ struct ReflectArgs {
     uint32_t reflectivity, bounces, mask, value;
 };
 
+// The kernels' form of a vr_atmosphere whose flags are not 0 (the colour bytes and the fog's span
+// are made here, once per call).
+vr::AtmosParams atmos_of(const vr_atmosphere* atm) {
+    return vr::atmos_params(atm->zenith, atm->horizon, atm->nadir, atm->up, atm->fog_color, atm->fog_start, atm->fog_end,
+                            atm->flags);
+}
+
 // One light pass per light over the rays of idx (null: all n), as vr_shade takes each light: the
 // render's lighting block in the primary walk's view.
 hipError_t light_terms(const vr_scene* s, vr_algo algo, const vr::KView& v, const vr_lighting* lights, size_t n_lights,
@@ -85,10 +94,11 @@ hipError_t light_terms(const vr_scene* s, vr_algo algo, const vr::KView& v, cons
 // Then the folds, deepest first.  All scratch is one allocation of sg's, cut into 256-byte aligned
 // parts -- the counts, the ray buffer(s), the record buffer, a list and a colour buffer per depth
 // asked for -- so the descent costs one hipMalloc and one hipFree whatever its depth (each costs
-// more than a depth's small kernels); it is freed on every path.
+// more than a depth's small kernels); it is freed on every path.  Under an atmosphere (at not null)
+// one atmosphere pass (vr_atmos.hip) follows each depth's last colour pass, over that depth's list.
 hipError_t reflect_descend(Staging& sg, const vr_scene* s, vr_algo algo, const vr::KView& v, const vr_lighting* lights,
-                           size_t n_lights, const float* ambient, const AoArgs* ao, const ReflectArgs& rf, const void* rays0,
-                           uint32_t n, void* state, uint32_t* colors0, hipStream_t st) {
+                           size_t n_lights, const float* ambient, const AoArgs* ao, const ReflectArgs& rf, const vr::AtmosParams* at,
+                           const void* rays0, uint32_t n, void* state, uint32_t* colors0, hipStream_t st) {
     const bool occlude = ao && ao->strength != 0u;       // (ao_out belongs to depth 0)
     const vr::KScene ks = vr::kscene(s);
     const auto part = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
@@ -127,6 +137,8 @@ hipError_t reflect_descend(Staging& sg, const vr_scene* s, vr_algo algo, const v
         if (e == hipSuccess) e = light_terms(s, algo, v, lights, n_lights, lj, c, state, col[j], st);
         if (occlude && ao->apply == VR_AO_ALL && e == hipSuccess)
             e = vr::launch_occlusion_apply((int)s->store, ks, rec, n, ao->strength, col[j], nullptr, st);
+        // (over the list alone: the state of a ray outside it is an earlier depth's)
+        if (at && e == hipSuccess) e = vr::launch_atmos_state(state, rays_j, lj, c, *at, v.translation, v.scale_f, col[j], st);
         rays_prev = rays_j;
     }
     for (uint32_t j = depth; j >= 1u && e == hipSuccess; --j)
@@ -145,7 +157,7 @@ hipError_t reflect_descend(Staging& sg, const vr_scene* s, vr_algo algo, const v
 int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights,
                  const float ambient[3], const float translation[3], uint32_t scale, const vr_ray* rays, size_t n,
                  int inputs_on_device, uint32_t* colors, vr_hit* hits, int outputs_on_device, uint32_t order, void* stream,
-                 const AoArgs* ao, const ReflectArgs* rf = nullptr) {
+                 const AoArgs* ao, const ReflectArgs* rf = nullptr, const vr_atmosphere* atm = nullptr) {
     const std::string who(who_c);
     if (!s) return fail(VR_E_INVALID, who + ": scene is NULL");
     if (!translation) return fail(VR_E_INVALID, who + ": translation NULL");
@@ -163,6 +175,8 @@ int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_li
     if (rf && rf->bounces > VR_MAX_BOUNCES) return fail(VR_E_INVALID, who + ": too many bounces (VR_MAX_BOUNCES)");
     if (rf && (rf->value & ~rf->mask) != 0u)
         return fail(VR_E_INVALID, who + ": mirror_value has bits outside mirror_mask (it could never match)");
+    if (atm && (atm->flags & ~(VR_ATMOS_SKY | VR_ATMOS_FOG)) != 0u)
+        return fail(VR_E_INVALID, who + ": unknown atmosphere flags");
     if (n == 0) return VR_OK;
     if (inputs_on_device && ((uintptr_t)rays & 15u) != 0u)
         return fail(VR_E_INVALID, who + ": device rays must be 16-byte aligned");
@@ -213,8 +227,15 @@ int shade_lights(const char* who_c, const vr_scene* s, vr_algo algo, const vr_li
     if (e == hipSuccess) e = light_terms(s, algo, v, lights, n_lights, idx, (uint32_t)n, state, dc, st);
     if (occlude && ao->apply == VR_AO_ALL && e == hipSuccess)
         e = vr::launch_occlusion_apply((int)s->store, vr::kscene(s), rec, (uint32_t)n, ao->strength, dc, da, st);
+    // the atmosphere over depth 0: elementwise over all n, so no order can matter
+    vr::AtmosParams at;
+    const bool tint = atm && atm->flags != 0u;
+    if (tint) at = atmos_of(atm);
+    if (tint && e == hipSuccess)
+        e = vr::launch_atmos_state(state, dr, nullptr, (uint32_t)n, at, v.translation, v.scale_f, dc, st);
     if (rf && rf->reflectivity != 0u && rf->bounces != 0u && e == hipSuccess) {
-        e = reflect_descend(sg, s, algo, v, lights, n_lights, ambient, ao, *rf, dr, (uint32_t)n, state, dc, st);
+        e = reflect_descend(sg, s, algo, v, lights, n_lights, ambient, ao, *rf, tint ? &at : nullptr, dr, (uint32_t)n, state,
+                            dc, st);
         if (e == hipErrorOutOfMemory) return fail(VR_E_NOMEM, who + ": reflection buffers: " + std::string(hipGetErrorString(e)));
     }
     if (e == hipSuccess && da && ao->out != da) {
@@ -394,6 +415,19 @@ int vr_shade_lights_reflect(const vr_scene* s, vr_algo algo, const vr_lighting* 
                         inputs_on_device, colors, hits, outputs_on_device, order, stream, &ao, &rf);
 }
 
+// vr_shade_lights_reflect under a sky and a distance fog (vr.h).
+int vr_shade_lights_atmosphere(const vr_scene* s, vr_algo algo, const vr_lighting* lights, size_t n_lights,
+                               const float ambient[3], const float translation[3], uint32_t scale, const vr_ray* rays,
+                               size_t n, int inputs_on_device, uint32_t* colors, vr_hit* hits, int outputs_on_device,
+                               uint32_t order, void* stream, uint32_t ao_strength, uint32_t ao_apply, uint32_t* ao_out,
+                               uint32_t reflectivity, uint32_t bounces, uint32_t mirror_mask, uint32_t mirror_value,
+                               const vr_atmosphere* atm) {
+    const AoArgs ao{ao_strength, ao_apply, ao_out};
+    const ReflectArgs rf{reflectivity, bounces, mirror_mask, mirror_value};
+    return shade_lights("vr_shade_lights_atmosphere", s, algo, lights, n_lights, ambient, translation, scale, rays, n,
+                        inputs_on_device, colors, hits, outputs_on_device, order, stream, &ao, &rf, atm);
+}
+
 // How open the face of each hit is at the hit point (vr.h).
 int vr_occlusion(const vr_scene* s, const vr_hit* hits, size_t n, int inputs_on_device, uint32_t* ao, int outputs_on_device,
                  void* stream) {
@@ -446,6 +480,57 @@ int vr_bounce_rays(int device, const float translation[3], uint32_t scale, const
     if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_bounce_rays: ray buffer");
     const hipError_t e = vr::launch_bounce_rays(dr, dh, (uint32_t)n, translation, (float)scale, dout, st);
     return finish(sg, e, out, dout, n * sizeof(vr_ray), "vr_bounce_rays");
+}
+
+// A daylight sky, fog off (vr.h).
+int vr_atmosphere_default(vr_atmosphere* atm) {
+    static_assert(sizeof(vr_atmosphere) == 76 && offsetof(vr_atmosphere, up) == 36 && offsetof(vr_atmosphere, fog_start) == 60 &&
+                      offsetof(vr_atmosphere, flags) == 68, "vr_atmosphere");
+    static_assert(vr::kAtmosSky == VR_ATMOS_SKY && vr::kAtmosFog == VR_ATMOS_FOG && vr::kAtmosStatusMiss == VR_HIT_MISS &&
+                      vr::kBounceStatusVoxel == VR_HIT_VOXEL, "VR_ATMOS_*, VR_HIT_*");
+    if (!atm) return fail(VR_E_INVALID, "vr_atmosphere_default: atm NULL");
+    const vr_atmosphere d = {{0.25f, 0.45f, 0.85f}, {0.75f, 0.85f, 0.95f}, {0.30f, 0.28f, 0.25f}, {0.0f, 1.0f, 0.0f},
+                             {0.75f, 0.85f, 0.95f}, 0.0f, 16.0f, VR_ATMOS_SKY, 0u};
+    *atm = d;
+    return VR_OK;
+}
+
+// The colour word of each ray under an atmosphere, from its hit record (vr.h): needs no scene.
+int vr_atmosphere_apply(int device, const vr_atmosphere* atm, const float translation[3], uint32_t scale, const vr_ray* rays,
+                        const vr_hit* hits, const uint32_t* colors_in, size_t n, int inputs_on_device, uint32_t* colors_out,
+                        int outputs_on_device, void* stream) {
+    if (!atm || !translation) return fail(VR_E_INVALID, "vr_atmosphere_apply: atm/translation NULL");
+    if ((atm->flags & ~(VR_ATMOS_SKY | VR_ATMOS_FOG)) != 0u) return fail(VR_E_INVALID, "vr_atmosphere_apply: unknown atmosphere flags");
+    if (n && (!rays || !hits || !colors_in || !colors_out))
+        return fail(VR_E_INVALID, "vr_atmosphere_apply: rays/hits/colors_in/colors_out NULL");
+    if (n >= (1ull << 31)) return fail(VR_E_INVALID, "vr_atmosphere_apply: too many records");
+    if (device < 0 || device > 63) return fail(VR_E_INVALID, "vr_atmosphere_apply: bad device");
+    if (n == 0) return VR_OK;
+    if (inputs_on_device && (((uintptr_t)rays | (uintptr_t)hits) & 15u) != 0u)
+        return fail(VR_E_INVALID, "vr_atmosphere_apply: device rays and hits must be 16-byte aligned");
+    if (inputs_on_device && ((uintptr_t)colors_in & 3u) != 0u)
+        return fail(VR_E_INVALID, "vr_atmosphere_apply: device colors_in must be 4-byte aligned");
+    if (outputs_on_device && ((uintptr_t)colors_out & 3u) != 0u)
+        return fail(VR_E_INVALID, "vr_atmosphere_apply: device colors_out must be 4-byte aligned");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(VR_E_INVALID, "vr_atmosphere_apply: no such device");
+    DeviceGuard dg(device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = vr::refuse_capture(st, "vr_atmosphere_apply")) return rc;
+    Staging sg(st);
+    const void *dr = rays, *dh = hits;
+    const uint32_t* din = colors_in;
+    if (!inputs_on_device) {
+        dr = sg.upload(rays, n * sizeof(vr_ray));
+        dh = sg.upload(hits, n * sizeof(vr_hit));
+        din = (const uint32_t*)sg.upload(colors_in, n * sizeof(uint32_t));
+    }
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_atmosphere_apply: record upload");
+    uint32_t* dout = outputs_on_device ? colors_out : (uint32_t*)sg.make(n * sizeof(uint32_t));
+    if (sg.err != hipSuccess) return hip_fail(sg.err, "vr_atmosphere_apply: colour buffer");
+    const vr::AtmosParams at = atmos_of(atm);
+    const hipError_t e = vr::launch_atmos_records(dr, dh, din, (uint32_t)n, at, translation, (float)scale, dout, st);
+    return finish(sg, e, colors_out, dout, n * sizeof(uint32_t), "vr_atmosphere_apply");
 }
 
 // The rays a render or pick walks for pixels of a frame (vr.h): needs no scene.

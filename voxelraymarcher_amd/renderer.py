@@ -218,11 +218,13 @@ class DeviceScene:
                      hits=hits, stream=stream)
 
     def shade_lights(self, algorithm, info, lights, rays, ambient=None, order=None, hits: bool = False, stream=None,
-                     ao=None, ao_apply=None, return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
-        """vr_shade_lights (or, with ao=, vr_shade_lights_ao; with reflect=, vr_shade_lights_reflect) with
-        this scene: see shade_lights()."""
+                     ao=None, ao_apply=None, return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None,
+                     atmosphere=None):
+        """vr_shade_lights (or, with ao=, vr_shade_lights_ao; with reflect=, vr_shade_lights_reflect; with
+        atmosphere=, vr_shade_lights_atmosphere) with this scene: see shade_lights()."""
         return shade_lights(self, algorithm, info, lights, rays, ambient=ambient, order=order, hits=hits, stream=stream,
-                            ao=ao, ao_apply=ao_apply, return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror)
+                            ao=ao, ao_apply=ao_apply, return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror,
+                            atmosphere=atmosphere)
 
     def occlusion(self, hits, stream=None):
         """vr_occlusion with this scene: see occlusion()."""
@@ -691,7 +693,7 @@ def occlusion(scene: DeviceScene, hits, stream=None):
 
 def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSceneInfo, lights, rays, ambient=None,
                  order: TraceOrder | None = None, hits: bool = False, stream=None, ao=None, ao_apply=None,
-                 return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
+                 return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None, atmosphere=None):
     """vr_shade_lights: shade() under several lights and an ambient term, from one primary walk per
     ray.  `lights` is a sequence of VrLighting blocks (at most VR_MAX_LIGHTS, possibly empty), each
     taken exactly as shade() takes its one; `ambient` is three floats or None.  colours[i] is, per
@@ -710,7 +712,12 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     and the words are blended from the back, (first * (255 - reflect) + deeper * reflect + 127) // 255
     per channel.  mirror = (mask, value): a voxel reflects when stored colour & mask == value; the
     default (None) is every voxel.  hits and the occlusion values stay those of the first hit.  With
-    reflect=None the call is the one above, and bounces and mirror must be left alone."""
+    reflect=None the call is the one above, and bounces and mirror must be left alone.
+    atmosphere (an Atmosphere, or None): vr_shade_lights_atmosphere -- at every depth a ray that misses
+    shows the sky in its direction (Atmosphere.SKY) and a hit is blended towards the fog's colour by
+    the length of its leg (Atmosphere.FOG), as atmosphere_apply() does it, before the depths are
+    blended; hits and the occlusion values stay as they are.  With atmosphere=None, or one whose
+    flags are 0, the call is the one above."""
     if ao is None and (return_ao or ao_apply is not None):
         raise ValueError("ao_apply and return_ao need ao= (a strength 0..255)")
     if reflect is None and (mirror is not None or int(bounces) != 1):
@@ -728,17 +735,22 @@ def shade_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, info: VoxelSc
     recs = _records(n, HIT_DTYPE, rays) if hits else None
     tail = (_ptr(rays), n, dev, _ptr(colors), _ptr(recs) if hits else None, dev,
             int(TraceOrder.AUTO if order is None else order), _stream_ptr(stream))
-    if reflect is not None:
+    if reflect is not None or atmosphere is not None:
         strength, apply = int(0 if ao is None else ao), int(AoApply.AMBIENT if ao_apply is None else ao_apply)
-        refl = (int(reflect), int(bounces)) + ((0, 0) if mirror is None else (int(mirror[0]), int(mirror[1])))
+        refl = (int(0 if reflect is None else reflect), int(0 if reflect is None else bounces))
+        refl += (0, 0) if mirror is None else (int(mirror[0]), int(mirror[1]))
         if any(not 0 <= x < 1 << 32 for x in (strength, apply) + refl):
             raise ValueError("reflect, bounces, mirror, ao and ao_apply must be unsigned 32-bit values")
         values = None
         if return_ao:
             values = torch.empty(n, dtype=torch.int32, device=rays.device) if dev else np.zeros(n, dtype=np.uint32)
         # (the library refuses what it refuses with its message, rays or none)
-        check(lib().vr_shade_lights_reflect(*args, *tail, strength, apply, _ptr(values) if return_ao else None, *refl),
-              "vr_shade_lights_reflect")
+        if atmosphere is not None:
+            check(lib().vr_shade_lights_atmosphere(*args, *tail, strength, apply, _ptr(values) if return_ao else None, *refl,
+                                                   ctypes.byref(_atmosphere_raw(atmosphere))), "vr_shade_lights_atmosphere")
+        else:
+            check(lib().vr_shade_lights_reflect(*args, *tail, strength, apply, _ptr(values) if return_ao else None, *refl),
+                  "vr_shade_lights_reflect")
         out = (colors,) + ((recs,) if hits else ()) + ((values,) if return_ao else ())
         return out if len(out) > 1 else colors
     if ao is None:
@@ -773,7 +785,7 @@ def _tile_order_pixels(width: int, height: int, device):
 
 def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Camera, info: VoxelSceneInfo, lights,
                   width: int, height: int, ambient=None, stream=None, samples: int = 1, ao=None, ao_apply=None,
-                  return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None):
+                  return_ao: bool = False, reflect=None, bounces: int = 1, mirror=None, atmosphere=None):
     """A width x height frame under several lights and an ambient term: shade_lights() of the
     frame's camera_rays(), as a (height, width) int32 CUDA tensor of 0x00RRGGBB words on the
     scene's device.  The rays are taken in 8 x 8-tile order (row-major rays measured 18-26 %
@@ -787,14 +799,16 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
     (height, width) int32 CUDA tensor -- of the fine frame's, (samples * height, samples * width),
     with samples > 1 (they are not filtered).
     reflect, bounces, mirror: shade_lights()'s mirror reflections, for every ray of the frame (of the
-    fine frame with samples > 1)."""
+    fine frame with samples > 1).
+    atmosphere: shade_lights()'s sky and distance fog, for every ray of the frame (of the fine frame
+    with samples > 1: the filter then blends sky and voxels along an edge)."""
     samples = int(samples)
     if samples != 1:
         if samples not in (2, 4, 8):
             raise ValueError("samples must be 1, 2, 4 or 8")
         fine = render_lights(scene, algorithm, camera, info, lights, samples * int(width), samples * int(height),
                              ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply, return_ao=return_ao,
-                             reflect=reflect, bounces=bounces, mirror=mirror)
+                             reflect=reflect, bounces=bounces, mirror=mirror, atmosphere=atmosphere)
         if return_ao:
             return resolve(fine[0], width, height, samples, stream=stream), fine[1]
         return resolve(fine, width, height, samples, stream=stream)
@@ -804,7 +818,7 @@ def render_lights(scene: DeviceScene, algorithm: RayMarchAlgorithm, camera: Came
         px, py = _tile_order_pixels(int(width), int(height), device)
         rays = camera_rays(camera, width, height, px, py, device=device.index, stream=stream)
         words = shade_lights(scene, algorithm, info, lights, rays, ambient=ambient, stream=stream, ao=ao, ao_apply=ao_apply,
-                             return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror)
+                             return_ao=return_ao, reflect=reflect, bounces=bounces, mirror=mirror, atmosphere=atmosphere)
         frame = torch.empty((int(height), int(width)), dtype=torch.int32, device=device)
         frame[py.long(), px.long()] = words[0] if return_ao else words
         if return_ao:
@@ -936,6 +950,90 @@ def bounce_rays(rays, hits, info: VoxelSceneInfo, device: int = 0, stream=None):
     if n:
         check(lib().vr_bounce_rays(int(device), f3(info.translation), int(info.scale), _ptr(rays), _ptr(hits), n, dev,
                                    _ptr(out), dev, _stream_ptr(stream)), "vr_bounce_rays")
+    return out
+
+
+class Atmosphere:
+    """vr_atmosphere: a sky and a linear distance fog, plain data (include/vr.h has the arithmetic).
+    zenith, horizon and nadir are the sky's colours (three floats each, 1.0 = 255) straight up,
+    level and straight down along `up` (not normalised by the library); a hit's word is blended
+    towards fog_color by (distance - fog_start) / (fog_end - fog_start), in world units.  flags is
+    Atmosphere.SKY | Atmosphere.FOG: what is applied.  Arguments left None keep
+    atmosphere_default()'s values: a daylight sky, up (0, 1, 0), fog off.  `raw` is the VrAtmosphere
+    block; changing it in place changes the next call."""
+    SKY, FOG = _capi.VR_ATMOS_SKY, _capi.VR_ATMOS_FOG
+
+    def __init__(self, zenith=None, horizon=None, nadir=None, up=None, fog_color=None, fog_start=None, fog_end=None,
+                 flags=None):
+        self.raw = _capi.VrAtmosphere()
+        check(lib().vr_atmosphere_default(ctypes.byref(self.raw)), "vr_atmosphere_default")
+        for name, value in (("zenith", zenith), ("horizon", horizon), ("nadir", nadir), ("up", up), ("fog_color", fog_color)):
+            if value is not None:
+                if len(value) != 3:
+                    raise ValueError(f"{name} must be three floats")
+                setattr(self.raw, name, f3(value))
+        if fog_start is not None:
+            self.raw.fog_start = float(fog_start)
+        if fog_end is not None:
+            self.raw.fog_end = float(fog_end)
+        if flags is not None:
+            if not 0 <= int(flags) < 1 << 32:
+                raise ValueError("flags must be an unsigned 32-bit value")
+            self.raw.flags = int(flags)
+
+    @property
+    def flags(self) -> int:
+        return int(self.raw.flags)
+
+
+def atmosphere_default() -> Atmosphere:
+    """vr_atmosphere_default: a daylight sky with up = (0, 1, 0), fog off, flags Atmosphere.SKY."""
+    return Atmosphere()
+
+
+def _atmosphere_raw(atmosphere) -> _capi.VrAtmosphere:
+    if isinstance(atmosphere, Atmosphere):
+        return atmosphere.raw
+    if isinstance(atmosphere, _capi.VrAtmosphere):
+        return atmosphere
+    raise TypeError("atmosphere must be an Atmosphere (or a VrAtmosphere block)")
+
+
+def atmosphere_apply(rays, hits, colors, info: VoxelSceneInfo, atmosphere, device: int = 0, stream=None):
+    """vr_atmosphere_apply: colors[i] under the atmosphere -- the sky in the direction of rays[i] where
+    hits[i] is a MISS (Atmosphere.SKY), colors[i] blended towards the fog's colour by the distance
+    from rays[i]'s origin to the hit point where it is a VOXEL record (Atmosphere.FOG), colors[i]
+    itself for everything else.  Records of pick(), trace(), shade() and shade_lights(), or made up.
+    numpy rays (a RAY_DTYPE array or (n, 6)) with a HIT_DTYPE array and n colour words give a uint32
+    numpy array; CUDA tensors -- float32 (n, 8) or (n, 6) rays, (n, 16) int32 records and an int32
+    (n,) tensor on one device -- give an int32 CUDA tensor there (`device` is then not used).  Needs
+    no scene."""
+    raw = _atmosphere_raw(atmosphere)
+    dev = int(hasattr(rays, "is_cuda") and rays.is_cuda)
+    if dev:
+        for t in (hits, colors):
+            if not (hasattr(t, "is_cuda") and t.is_cuda) or t.device != rays.device:
+                raise TypeError("rays, hits and colors must all be CUDA tensors on one device, or all numpy arrays")
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 16:
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        if colors.dtype not in (torch.int32, torch.uint32) or colors.dim() != 1:
+            raise TypeError("colors must be an int32 or uint32 CUDA tensor of shape (n,)")
+        rays, hits, colors = _rays_cuda(rays), hits.contiguous(), colors.contiguous()
+        device = rays.device.index
+        out = torch.empty(colors.shape[0], dtype=torch.int32, device=rays.device)
+    else:
+        if not (isinstance(hits, np.ndarray) and hits.dtype == HIT_DTYPE):
+            raise TypeError("hits must be a HIT_DTYPE array or an (n, 16) int32 CUDA tensor")
+        rays, hits = _rays_numpy(rays), np.ascontiguousarray(hits).reshape(-1)
+        colors = np.ascontiguousarray(colors, dtype=np.uint32).reshape(-1)
+        out = np.zeros(colors.shape[0], dtype=np.uint32)
+    n = rays.shape[0]
+    if hits.shape[0] != n or colors.shape[0] != n:
+        raise ValueError("rays, hits and colors lengths differ")
+    if n or raw.flags & ~(_capi.VR_ATMOS_SKY | _capi.VR_ATMOS_FOG):    # (the library refuses unknown flags, with its message)
+        check(lib().vr_atmosphere_apply(int(device), ctypes.byref(raw), f3(info.translation), int(info.scale), _ptr(rays),
+                                        _ptr(hits), _ptr(colors), n, dev, _ptr(out), dev, _stream_ptr(stream)),
+              "vr_atmosphere_apply")
     return out
 
 
